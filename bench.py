@@ -10,7 +10,11 @@ ranks also the RCCL gather of the 16-byte per-pair result records to rank 0
 (db sharded).  value = all ranks' cells / max-over-ranks
 wall time.
 
-The other BASELINE.json configs ride along as extra keys under "configs"
+A plain run does only what the headline needs: set up, warm up, time the
+steps, write the outputs (--dump-outputs DIR) and print the line.  With
+--full it also checks the last step's output against the oracle, times the
+fill alone, runs the CPU baseline, and the other BASELINE.json configs ride
+along as extra keys under "configs"
 (SURVEY.md §8(d)), each timed here so the driver's clock covers them, each
 with its own `roofline` (the dominant kernel against the HBM or VALU peak)
 and `cpu_baseline`:
@@ -31,7 +35,15 @@ and `cpu_baseline`:
   cli       the drop-in CLI end to end on a 316 x 316-record FASTA of 150 bp
       (batched render, reference text per pair; process wall time) (N = 1).
 
-    python bench.py --gpus N --steps K --warmup W [--legs c2_full,c5,c1,c3,c3_affine,c4,c4_spans,host,cli|none]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full [--legs c2_full,c5,c1,c3,c3_affine,c4,c4_spans,host,cli|none]
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers (rank 0's) as float64 .npy files: results.npy, one row per pair
+(score, status, cigar_len, end_states, printed, flags), and, unless
+--score-only, cigar_pairs.npy and cigar_words.npy, a seeded sample of pairs
+and each one's CIGAR words (length << 4 | op; -1 past cigar_len); with N > 1
+also results_gathered.npy, every rank's rows as rank 0 received them.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts
 the N ranks itself (torch.distributed.run on 127.0.0.1, as a child process;
@@ -250,6 +262,41 @@ def verify_c2(res_np, cig_np, cigar_off, qs, qo, ds, do, n_check: int = 1000) ->
             ok = np.array_equal(cig_np[o0:o0 + int(r["cigar_len"][k])], want.cigar_words(k))
         bad += not ok
     return {"pairs": n, "mismatches": bad, "checker": "oracle/refcheck.c (untimed)"}
+
+
+DUMP_CIGAR_PAIRS = 8192  # pairs of --dump-outputs' CIGAR sample (x (LQ + LD) words x 8 B: 20 MB)
+
+
+def result_rows(res_np) -> np.ndarray:
+    """saln_nw_result records as float64 rows (score, status, cigar_len,
+    end_states, printed, flags)."""
+    from sequencealigning_amd import _lib
+    r = res_np.view(_lib.RESULT_DTYPE)
+    return np.stack([r[f].astype(np.float64) for f in
+                     ("score", "status", "cigar_len", "end_states", "printed", "flags")], 1)
+
+
+def dump_outputs(path: str, res_np, cig_np=None, cigar_off=None, gathered=None) -> None:
+    """--dump-outputs: the last timed step's result records of every pair
+    and, of a seeded sample of DUMP_CIGAR_PAIRS pairs, the CIGAR words."""
+    os.makedirs(path, exist_ok=True)
+    rows = result_rows(res_np)
+    np.save(os.path.join(path, "results.npy"), rows)
+    if gathered is not None:
+        np.save(os.path.join(path, "results_gathered.npy"),
+                np.stack([result_rows(g) for g in gathered]))
+    if cig_np is None:
+        return
+    n = len(rows)
+    sel = np.sort(np.random.default_rng(SEED).choice(n, min(n, DUMP_CIGAR_PAIRS), replace=False))
+    cap = int(np.max(np.diff(np.asarray(cigar_off, np.int64)))) if n else 0
+    words = np.full((len(sel), cap), -1.0)
+    for row, k in enumerate(sel):
+        m = int(rows[k, 2]) if rows[k, 4] else 0
+        o0 = int(cigar_off[k])
+        words[row, :m] = cig_np[o0:o0 + m]
+    np.save(os.path.join(path, "cigar_pairs.npy"), sel.astype(np.float64))
+    np.save(os.path.join(path, "cigar_words.npy"), words)
 
 
 def timed(fn, world, dist, torch, local):
@@ -1133,11 +1180,16 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=N_PAIRS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle check of its output, the fill alone, "
+                         "the extra configs (--legs) and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--legs", default="auto",
-                    help="comma list of extra configs (c2_full,c5,c1,c3,c3_affine,c4,c4_spans,host,"
-                         "cli,cli_all; c4_sharded at N > 1), 'none', or 'auto' (all at N = 1, "
-                         "c5 and c4_sharded at N > 1)")
+                    help="with --full: comma list of extra configs (c2_full,c5,c1,c3,c3_affine,c4,"
+                         "c4_spans,host,cli,cli_all; c4_sharded at N > 1), 'none', or 'auto' (all "
+                         "at N = 1, c5 and c4_sharded at N > 1)")
     ap.add_argument("--score-only", action="store_true",
                     help="score + panic status only (no parent codes / traceback; the C5 mode)")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false",
@@ -1153,6 +1205,10 @@ def main() -> None:
         sys.exit(f"bench.py: {', '.join(bad)} set in the environment; the bench measures the "
                  f"product library sequencealigning_amd/libsaln.so with its default options "
                  f"(allowed SALN_* variables: {', '.join(ALLOWED_ENV) or 'none'})")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if not args.full and args.legs not in ("auto", "none"):
+        sys.exit(f"bench.py: --legs {args.legs} needs --full (a plain run times the headline only)")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -1174,7 +1230,9 @@ def main() -> None:
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group(args.backend, device_id=torch.device("cuda", local))
-    if args.legs == "auto":
+    if not args.full:
+        legs = []
+    elif args.legs == "auto":
         legs = list(ALL_LEGS) if world == 1 else ["c5", "c4_sharded"]
     elif args.legs == "none":
         legs = []
@@ -1249,10 +1307,20 @@ def main() -> None:
                          wall_s=local_dt / max(1, args.steps))
     cells_rank = plan.cells
     total_cells = cells_rank * world * args.steps
-    # outside the timed region: the fill alone (sequential executes), so the
-    # line carries the kernel's own duration beside its co-run one
+    # the last timed step's outputs, before anything else runs on the plan
+    hr = hcig = None
+    if rank == 0:
+        last = (args.steps - 1) % nbuf
+        hr = res[last].cpu().numpy()
+        if not args.score_only and (args.full or args.dump_outputs):
+            hcig = cig[last].cpu().numpy().view(np.uint32)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hr, hcig, plan.cigar_off,
+                         [g.cpu().numpy() for g in gathered] if gathered else None)
+    # --full, outside the timed region: the fill alone (sequential executes),
+    # so the line carries the kernel's own duration beside its co-run one
     fill_alone_s = None
-    if pipelined and rank == 0:
+    if args.full and pipelined and rank == 0:
         plan.set_async(False)
         plan.set_timing(True)
         for _ in range(5):
@@ -1265,8 +1333,6 @@ def main() -> None:
     fill_avg_s = fill_ms / max(1, fill_n) / 1e3
     out = None
     if rank == 0:
-        last = (args.steps - 1) % nbuf if args.steps else 0
-        hr = res[last].cpu().numpy()
         statuses = np.bincount(hr[1::4] & 0xFF, minlength=3)
         # 8 x 19 groups, 4-bit walk codes (table penalties unless nw.pk_tab = 0)
         fill_kernel = ("nw_fill_pk_tab_kernel<8, 19," if saln._lib.get_option("nw.pk_tab")[0]
@@ -1285,8 +1351,8 @@ def main() -> None:
                                     if fill_alone_s else None),
                         note=("pipelined: each fill co-runs with the previous step's traceback, "
                               "so kernel_avg_ms is the fill's co-run duration; "
-                              "kernel_avg_ms_alone / frac_alone: 5 sequential executes after "
-                              "the timed region; step_frac = algorithmic bytes per step / "
+                              "kernel_avg_ms_alone / frac_alone (--full): 5 sequential executes "
+                              "after the timed region; step_frac = algorithmic bytes per step / "
                               "ms_per_step / peak; algorithmic bytes = 1 B/cell (the parent "
                               "set, SURVEY 8(d)): the fill stores 4-bit walk codes, so its "
                               "written bytes (traffic) are below it") if pipelined else None,
@@ -1320,14 +1386,13 @@ def main() -> None:
                                         "from hipEvents; gather_ms: one dist.gather of its "
                                         "records to rank 0 (RCCL), probed after the timed "
                                         "region; wall_ms: the rank's own timed wall per step"}
-        if not args.score_only:
-            out["verified"] = verify_c2(hr, cig[last].cpu().numpy().view(np.uint32),
-                                        plan.cigar_off, qs, qo, ds, do)
+        if args.full and not args.score_only:
+            out["verified"] = verify_c2(hr, hcig, plan.cigar_off, qs, qo, ds, do)
     plan.close()
     del res, cig, dq, dd
     torch.cuda.empty_cache()
 
-    cpu = not args.no_cpu_baseline
+    cpu = args.full and not args.no_cpu_baseline
     extra = {}
     for leg in legs:
         t0 = time.perf_counter()

@@ -60,6 +60,51 @@ def test_bench_refuses_leftover_experiment_variables():
     assert bench.refused_env({k: "1" for k in bench.ALLOWED_ENV}) == []
 
 
+def test_plain_run_refuses_named_legs():
+    """The extra configs run only with --full: a plain run that names legs
+    stops before it touches the GPU instead of dropping them silently."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "c5"],
+                       capture_output=True, text=True, env=_env(), timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr, r.stderr[-500:]
+
+
+def test_dump_outputs_layout(tmp_path):
+    """--dump-outputs: every pair's result record as a float64 row, and a
+    seeded sample of pairs with each one's CIGAR words, -1 past cigar_len and
+    for pairs that printed nothing; the same sample on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from sequencealigning_amd import _lib
+    n, cap = bench.DUMP_CIGAR_PAIRS + 100, 7
+    rng = np.random.default_rng(1)
+    r = np.zeros(n, dtype=_lib.RESULT_DTYPE)
+    r["score"] = rng.integers(-500, 500, n)
+    r["status"] = rng.choice([0, 2], n)
+    r["cigar_len"] = rng.integers(1, cap + 1, n)
+    r["printed"] = r["status"] == 0
+    r["end_states"] = rng.integers(0, 8, n)
+    off = np.arange(n + 1, dtype=np.uint64) * np.uint64(cap)
+    cig = rng.integers(0, 1 << 32, n * cap, dtype=np.uint64).astype(np.uint32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), r.view(np.int32), cig, off)
+    rows = np.load(tmp_path / "a" / "results.npy")
+    assert rows.dtype == np.float64 and rows.shape == (n, 6)
+    for col, f in enumerate(("score", "status", "cigar_len", "end_states", "printed", "flags")):
+        assert np.array_equal(rows[:, col], r[f].astype(np.float64)), f
+    sel = np.load(tmp_path / "a" / "cigar_pairs.npy").astype(np.int64)
+    words = np.load(tmp_path / "a" / "cigar_words.npy")
+    assert len(sel) == bench.DUMP_CIGAR_PAIRS == len(set(sel)) and words.shape == (len(sel), cap)
+    for row, k in enumerate(sel):
+        m = int(r["cigar_len"][k]) if r["printed"][k] else 0
+        assert np.array_equal(words[row, :m], cig[k * cap:k * cap + m].astype(np.float64))
+        assert np.all(words[row, m:] == -1)
+    for f in ("results.npy", "cigar_pairs.npy", "cigar_words.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    bench.dump_outputs(str(tmp_path / "c"), r.view(np.int32))  # --score-only: records alone
+    assert sorted(os.listdir(tmp_path / "c")) == ["results.npy"]
+
+
 def _c4_sharded_worker(rank, world, port, q, d, out):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -14,7 +14,7 @@ step() { local name=$1 lim=$2; shift 2; timeout -k 10 $lim "$@" > $O/$name.log 2
   step tests 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
   tail -1 $O/tests.log
 }
-step bench 900 python bench.py --steps 20 --warmup 3
+step bench 900 python bench.py --steps 20 --warmup 3 --full
 tail -1 $O/bench.log | cut -c1-600
 step prof_c2 600 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --legs none
 step prof_c4 600 rocprofv3 --kernel-trace --stats -d $O/prof_c4 -o run --output-format csv -- python3 tools/bench_long.py --len 100000 --reps 10

@@ -2,7 +2,7 @@
 # Round-3 GPU steps.  STAGES (space-separated, default "smoke tests bench"):
 #   smoke  __graft_entry__.smoke()
 #   tests  pytest -m gpu (TESTS= narrows it: a path or -k expression args)
-#   bench  bench.py --steps 20 --warmup 3 (BENCH_ARGS= extra args)
+#   bench  bench.py --steps 20 --warmup 3 --full (BENCH_ARGS= extra args)
 #   prof   rocprofv3 --kernel-trace --stats of the headline command
 #   proflegs  the same over tools/prof_legs.py (the legs' GPU workloads)
 #   pmc    PMC passes (tools/pmc.sh) of the headline workload -> pmc_traffic.json
@@ -19,7 +19,7 @@ for st in ${STAGES:-smoke tests bench}; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1100 python -u -m pytest ${TESTS:-tests} -m gpu -x -q --timeout 300 --timeout-method thread
            tail -3 $O/tests.log ;;
-    bench) step bench 900 python bench.py --steps 20 --warmup 3 $BENCH_ARGS
+    bench) step bench 900 python bench.py --steps 20 --warmup 3 --full $BENCH_ARGS
            tail -1 $O/bench.log | cut -c1-900 ;;
     prof)  step prof_c2 600 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --legs none ;;
     proflegs) step prof_legs 900 rocprofv3 --kernel-trace --stats -d $O/prof_legs -o run --output-format csv -- python3 tools/prof_legs.py --legs ${PROF_LEGS:-c1,c3,c3_affine,c4,c5} ;;

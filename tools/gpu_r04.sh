@@ -12,7 +12,7 @@
 #   clileg   bench.py's cli leg alone (with its stage breakdown)
 #   smoke    __graft_entry__.smoke()
 #   tests    pytest -m gpu (TESTS= narrows it)
-#   bench    bench.py --steps 20 --warmup 3 (BENCH_ARGS= extra args)
+#   bench    bench.py --steps 20 --warmup 3 --full (BENCH_ARGS= extra args)
 #   prof     rocprofv3 --kernel-trace --stats of the headline command
 #   proflegs the same over tools/prof_legs.py
 #   pmc      PMC passes (tools/pmc.sh) of the headline workload -> pmc_traffic.json
@@ -117,7 +117,7 @@ for st in ${STAGES:-smoke tests bench}; do
           grep -v amdgpu.ids $O/ablone8_${w}_$i.log | python3 -c "import sys,json; [print('lone=$w', l.split()[1], json.loads(l[l.index('{'):])['fill_ms'], json.loads(l[l.index('{'):])['walk_ms']) for l in sys.stdin if '{' in l]"
         done
       done
-      step spanleg 600 python bench.py --steps 2 --warmup 1 --legs c4,c4_spans --no-cpu-baseline
+      step spanleg 600 python bench.py --steps 2 --warmup 1 --full --legs c4,c4_spans --no-cpu-baseline
       tail -1 $O/spanleg.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); v=d['configs']['c4_spans']; print(v['fill_ms'], v['walk_ms'])" ;;
     abbase)  # SALN_LIB=libsaln_base.so (an earlier tree) against the in-tree library
       for i in ${REPS:-1 2 3}; do
@@ -208,12 +208,12 @@ for st in ${STAGES:-smoke tests bench}; do
           tail -1 $O/abtabp_${w}_$i.log | cut -c1-220
         done
       done ;;
-    clileg) step clileg 600 python bench.py --steps 2 --warmup 1 --legs cli
+    clileg) step clileg 600 python bench.py --steps 2 --warmup 1 --full --legs cli
             tail -1 $O/clileg.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps(d['configs']['cli']))" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1100 python -u -m pytest ${TESTS:-tests} -m gpu -x -q --timeout 300 --timeout-method thread
            tail -3 $O/tests.log ;;
-    bench) step bench 900 python bench.py --steps 20 --warmup 3 $BENCH_ARGS
+    bench) step bench 900 python bench.py --steps 20 --warmup 3 --full $BENCH_ARGS
            tail -1 $O/bench.log | cut -c1-1500 ;;
     prof)  step prof_c2 600 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --legs none ;;
     proflegs) step prof_legs 900 rocprofv3 --kernel-trace --stats -d $O/prof_legs -o run --output-format csv -- python3 tools/prof_legs.py --legs ${PROF_LEGS:-c1,c3,c3_affine,c4,c5} ;;

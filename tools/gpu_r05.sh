@@ -6,7 +6,7 @@
 #            (an earlier commit's build), sequential and pipelined, REPS alternations
 #   smoke    __graft_entry__.smoke()
 #   tests    pytest -m gpu (TESTS= narrows it, e.g. "tests/test_span_gpu.py -k xcd")
-#   bench    bench.py --steps 20 --warmup 3 (BENCH_ARGS= extra args)
+#   bench    bench.py --steps 20 --warmup 3 --full (BENCH_ARGS= extra args)
 #   prof     rocprofv3 --kernel-trace --stats of the headline command (pipelined),
 #            its fills split into co-run / alone by tools/trace_overlap.py
 #   profseq  the same with --no-pipeline (every fill alone)
@@ -59,7 +59,7 @@ for st in ${STAGES:-smoke tests bench}; do
            tail -3 $O/smoke.log ;;
     tests) step tests 1500 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 300 --timeout-method thread
            tail -3 $O/tests.log ;;
-    bench) step bench 600 python bench.py --steps 20 --warmup 3 $BENCH_ARGS
+    bench) step bench 600 python bench.py --steps 20 --warmup 3 --full $BENCH_ARGS
            tail -1 $O/bench.log | cut -c1-3000 ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --legs none --no-cpu-baseline
           find $O/prof -name '*kernel_stats.csv' -exec head -12 {} \; | cut -c1-220

@@ -10,7 +10,7 @@
 #   smoke    __graft_entry__.smoke()
 #   tests    pytest -m gpu (TESTS= narrows it to files, KEXPR= to a -k expression)
 #   chains   tools/micro/row_chains (row-fill chains per wave)
-#   bench    bench.py --steps 20 --warmup 3 (BENCH_ARGS= extra args)
+#   bench    bench.py --steps 20 --warmup 3 --full (BENCH_ARGS= extra args)
 #   prof     rocprofv3 --kernel-trace --stats of the headline command (pipelined),
 #            its fills split into co-run / alone by tools/trace_overlap.py
 #   profseq  the same with --no-pipeline (every fill alone)
@@ -86,7 +86,7 @@ for st in ${STAGES:-smoke tests bench}; do
         step wfa2_cur_$i 300 python tools/bench_wfa_affine.py --pairs 200000
         tail -1 $O/wfa2_cur_$i.log
       done ;;
-    c2full) step c2full 400 python bench.py --steps 5 --warmup 2 --legs c2_full --no-cpu-baseline
+    c2full) step c2full 400 python bench.py --steps 5 --warmup 2 --full --legs c2_full --no-cpu-baseline
             tail -1 $O/c2full.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps(d['configs']['c2_full'])[:1500])" ;;
     chains) step chains 300 tools/micro/row_chains
             cat $O/chains.log ;;
@@ -98,7 +98,7 @@ for st in ${STAGES:-smoke tests bench}; do
              step tests 1500 python -u -m pytest ${TESTS:-tests} -m gpu -x -v --timeout 300 --timeout-method thread
            fi
            tail -3 $O/tests.log ;;
-    bench) step bench 600 python bench.py --steps 20 --warmup 3 $BENCH_ARGS
+    bench) step bench 600 python bench.py --steps 20 --warmup 3 --full $BENCH_ARGS
            tail -1 $O/bench.log | cut -c1-3000 ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --legs none --no-cpu-baseline
           find $O/prof -name '*kernel_stats.csv' -exec head -12 {} \; | cut -c1-220

@@ -14,12 +14,15 @@ if [[ $STEP == all || $STEP == test ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1 || { echo "pytest gpu failed rc=$?"; tail -40 gpurun_out/pytest_gpu.log; exit 1; }
   tail -3 gpurun_out/pytest_gpu.log
 fi
+# the bench and profile steps write under $OUT_DIR (default build/evidence)
+O=${OUT_DIR:-build/evidence}
+mkdir -p "$O"
 if [[ $STEP == all || $STEP == bench ]]; then
-  timeout -k 10 600 python bench.py --steps 10 --warmup 3 > gpurun_out/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 gpurun_out/bench.log; exit 1; }
-  tail -1 gpurun_out/bench.log
+  timeout -k 10 600 python bench.py --steps 10 --warmup 3 --full > $O/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -30 $O/bench.log; exit 1; }
+  tail -1 $O/bench.log
 fi
 if [[ $STEP == all || $STEP == prof ]]; then
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/prof.log 2>&1 || { echo "rocprof failed rc=$?"; tail -30 gpurun_out/prof.log; exit 1; }
-  find gpurun_out/prof -name "*kernel_stats.csv" | head -3
-  for f in $(find gpurun_out/prof -name "*kernel_stats.csv"); do head -5 "$f"; done
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/prof.log 2>&1 || { echo "rocprof failed rc=$?"; tail -30 $O/prof.log; exit 1; }
+  find $O/prof -name "*kernel_stats.csv" | head -3
+  for f in $(find $O/prof -name "*kernel_stats.csv"); do head -5 "$f"; done
 fi
