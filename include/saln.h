@@ -64,7 +64,15 @@ typedef enum {
                                       stripe walk fell back to the sequential walker */
 
 /* ScoringScheme, needleman_wunsch_affine.rs:15-20 / :382-388.
- * NULL everywhere means the reference SCHEME {5, -4, -8, -6}. */
+ * NULL everywhere means the reference SCHEME {5, -4, -8, -6}.
+ * The scheme only selects the kernel (packed int16 where the range guards
+ * hold, int32 otherwise), never the result: the reference recurrences' with
+ * these four values.  Checked against the CPU oracle for match and mismatch
+ * of either sign and relative order, gap_open of either sign and
+ * gap_extend <= 0; a positive gap_extend is accepted but
+ * covered by no test.  A pair so long, or penalties so large, that its
+ * scores could leave the engine's int32 range is refused with SALN_E_INVALID
+ * by every entry point. */
 typedef struct {
     int32_t match;      /* +5 */
     int32_t mismatch;   /* -4 */
@@ -298,6 +306,23 @@ int saln_nw_plan_status(saln_nw_plan *plan, uint32_t *flags);
  * (default 2^24, each poll sleeping ~64 clocks).  Test hook: 0 makes any wait
  * that finds its row unpublished fail, which injects SALN_FLAG_WAIT_TIMEOUT. */
 int saln_nw_plan_set_wait_limit(saln_nw_plan *plan, uint32_t polls);
+/* Introspection for tests: what the next saln_nw_execute does with pair
+ * `pair` (results index), from the code that launches it (no second copy of
+ * the decision).  The launch-wide fields depend on the longest db among the
+ * plan's pairs of the same variant, on the plan's mode (score-only, async)
+ * and on the options the plan read at creation. */
+typedef struct {
+    int32_t variant;   /* fill variant number (nw_kernels.hip's; -1: a pair with an
+                          empty side, which no fill runs) */
+    int32_t packed;    /* 1: int16 halves, two pairs per lane group; 0: i32 lanes */
+    int32_t rebase;    /* 1: the packed launch uses the rebasing int16 frame */
+    int32_t table;     /* packed launch body: 0 generic, 2 table at scale 2, 4 table at
+                          scale 4, 3 row profiles */
+    int32_t stripe_pk; /* column-stripe pairs (variant 3): 1 packed stripes */
+    int32_t rows_k;    /* column-stripe pairs: the row fill's columns per lane
+                          (0: the skewed or the packed stripe fill) */
+} saln_nw_pair_path;
+int saln_nw_plan_pair_path(const saln_nw_plan *plan, uint64_t pair, saln_nw_pair_path *out);
 /* Waits for the device, then returns the plan's blocks to its context. */
 int saln_nw_plan_destroy(saln_nw_plan *plan);
 

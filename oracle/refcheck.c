@@ -24,6 +24,7 @@ typedef struct {
     int32_t *cig_len;
     uint32_t *cig;
     uint64_t lo, hi;
+    const ref_nw_scoring *sc;
     int failed;
 } CheckSlice;
 
@@ -42,7 +43,7 @@ static void *check_worker(void *arg) {
         const uint8_t *q = s->qs + s->qo[p], *d = s->ds + s->dof[p];
         const size_t lq = s->qo[p + 1] - s->qo[p], ld = s->dof[p + 1] - s->dof[p];
         ref_nw_mats m;
-        if (ref_nw_fill(q, lq, d, ld, &m) != 0) {
+        if (ref_nw_fill_s(q, lq, d, ld, s->sc, &m) != 0) {
             s->failed = 1;
             return NULL;
         }
@@ -80,6 +81,14 @@ int ref_nw_check_pairs_mt(const uint8_t *qs, const uint64_t *q_off, const uint8_
                           const uint64_t *d_off, uint64_t n_pairs, const uint64_t *cig_off,
                           int32_t *score, uint8_t *end_states, uint8_t *panics, int32_t *cig_len,
                           uint32_t *cig, int threads) {
+    return ref_nw_check_pairs_mt_s(qs, q_off, ds, d_off, n_pairs, cig_off, &ref_nw_default_scoring,
+                                   score, end_states, panics, cig_len, cig, threads);
+}
+
+int ref_nw_check_pairs_mt_s(const uint8_t *qs, const uint64_t *q_off, const uint8_t *ds,
+                            const uint64_t *d_off, uint64_t n_pairs, const uint64_t *cig_off,
+                            const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                            uint8_t *panics, int32_t *cig_len, uint32_t *cig, int threads) {
     if (threads < 1) threads = 1;
     if (threads > 256) threads = 256;
     pthread_t th[256];
@@ -87,7 +96,7 @@ int ref_nw_check_pairs_mt(const uint8_t *qs, const uint64_t *q_off, const uint8_
     for (int t = 0; t < threads; ++t) {
         CheckSlice c = {qs, ds, q_off, d_off, cig_off, score, end_states, panics, cig_len, cig,
                         n_pairs * (uint64_t)t / (uint64_t)threads,
-                        n_pairs * (uint64_t)(t + 1) / (uint64_t)threads, 0};
+                        n_pairs * (uint64_t)(t + 1) / (uint64_t)threads, sc, 0};
         sl[t] = c;
         pthread_create(&th[t], NULL, check_worker, &sl[t]);
     }

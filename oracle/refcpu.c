@@ -9,17 +9,21 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* SCHEME, needleman_wunsch_affine.rs:15-20 */
-#define GO (-8)
-#define GE (-6)
-#define MIS (-4)
-#define MAT 5
+/* SCHEME, needleman_wunsch_affine.rs:15-20: the reference's constants; the
+ * _s entry points take any other four values in their place */
+const ref_nw_scoring ref_nw_default_scoring = {5, -4, -8, -6};
 
 enum { ST_M = 0, ST_I = 1, ST_D = 2 }; /* State, :365-371 */
 
 static inline int32_t max2(int32_t a, int32_t b) { return a > b ? a : b; }
 
 int ref_nw_fill(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, ref_nw_mats *o) {
+    return ref_nw_fill_s(q, lq, d, ld, &ref_nw_default_scoring, o);
+}
+
+int ref_nw_fill_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld,
+                  const ref_nw_scoring *sc, ref_nw_mats *o) {
+    const int32_t MAT = sc->match, MIS = sc->mismatch, GO = sc->gap_open, GE = sc->gap_extend;
     const size_t W = lq + 1, H = ld + 1, n = W * H;
     memset(o, 0, sizeof(*o));
     o->lq = lq;

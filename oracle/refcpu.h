@@ -43,8 +43,20 @@ typedef struct {
     uint8_t *pM, *pI, *pD;
 } ref_nw_mats;
 
+/* Scoring scheme of the _s entry points: the reference recurrences with its
+ * four SCHEME constants (:15-20) replaced; the sentinel, the i32 arithmetic,
+ * the boundary formulas (i+1)*ge + go, the parent-set tie rules and the DFS
+ * push order stay.  Every entry point without the suffix passes
+ * ref_nw_default_scoring = {5, -4, -8, -6}. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+} ref_nw_scoring;
+extern const ref_nw_scoring ref_nw_default_scoring;
+
 /* Allocate and fill; returns 0 on success.  Free with ref_nw_free. */
 int ref_nw_fill(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, ref_nw_mats *out);
+int ref_nw_fill_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld,
+                  const ref_nw_scoring *sc, ref_nw_mats *out);
 void ref_nw_free(ref_nw_mats *m);
 
 /* Dense 7-bit cell code used for mask parity (same meaning as the product's
@@ -110,12 +122,19 @@ int ref_nw_check_pairs_mt(const uint8_t *qs, const uint64_t *q_off, const uint8_
                           const uint64_t *d_off, uint64_t n_pairs, const uint64_t *cig_off,
                           int32_t *score, uint8_t *end_states, uint8_t *panics, int32_t *cig_len,
                           uint32_t *cig, int threads);
+int ref_nw_check_pairs_mt_s(const uint8_t *qs, const uint64_t *q_off, const uint8_t *ds,
+                            const uint64_t *d_off, uint64_t n_pairs, const uint64_t *cig_off,
+                            const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                            uint8_t *panics, int32_t *cig_len, uint32_t *cig, int threads);
 
 /* Linear-memory score + end states + panic status of one pair with the
  * reference semantics (reflinear.c), on `threads` column stripes.  For
  * pairs too large for ref_nw_fill (C4).  Returns 0 on success. */
 int ref_nw_score_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
                         int32_t *score, uint8_t *end_states, int *panics);
+int ref_nw_score_linear_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
+                          const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                          int *panics);
 
 /* ref_nw_score_linear plus the first event of the reference DFS over stored
  * parent sets (1 B per cell of host memory): ops (forward, '=' 'X' 'I' 'D')
@@ -125,6 +144,10 @@ int ref_nw_score_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld
 int ref_nw_first_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
                         int32_t *score, uint8_t *end_states, int *panics, char *ops,
                         size_t ops_cap, int64_t *ops_len, uint64_t *dead_nodes);
+int ref_nw_first_linear_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
+                          const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                          int *panics, char *ops, size_t ops_cap, int64_t *ops_len,
+                          uint64_t *dead_nodes);
 
 /* FASTA parser restatement (parse.rs:54-99) on an in-memory buffer.
  * has_valid_ext: result of the extension check (:55-60) done by the caller.

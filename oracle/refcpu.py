@@ -24,6 +24,20 @@ def build() -> str:
     return _LIB_PATH
 
 
+class _Scoring(C.Structure):
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32),
+                ("gap_open", C.c_int32), ("gap_extend", C.c_int32)]
+
+
+DEFAULT_SCORING = (5, -4, -8, -6)  # (match, mismatch, gap_open, gap_extend)
+
+
+def _scoring(scoring):
+    """(match, mismatch, gap_open, gap_extend), or None for the reference's scheme."""
+    m, x, go, ge = DEFAULT_SCORING if scoring is None else scoring
+    return _Scoring(int(m), int(x), int(go), int(ge))
+
+
 class _Mats(C.Structure):
     _fields_ = [("lq", C.c_size_t), ("ld", C.c_size_t),
                 ("M", C.POINTER(C.c_int32)), ("I", C.POINTER(C.c_int32)),
@@ -40,6 +54,8 @@ def lib():
         L = C.CDLL(_LIB_PATH)
         u8p = C.POINTER(C.c_uint8)
         L.ref_nw_fill.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.POINTER(_Mats)]
+        scp = C.POINTER(_Scoring)
+        L.ref_nw_fill_s.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, scp, C.POINTER(_Mats)]
         L.ref_nw_free.argtypes = [C.POINTER(_Mats)]
         L.ref_nw_dense_mask.argtypes = [C.POINTER(_Mats), u8p]
         L.ref_nw_score.argtypes = [C.POINTER(_Mats), u8p]
@@ -76,6 +92,17 @@ def lib():
                                             C.POINTER(C.c_uint64), C.c_uint64,
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_int32), u8p, u8p,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int]
+        L.ref_nw_check_pairs_mt_s.argtypes = [u8p, C.POINTER(C.c_uint64), u8p,
+                                              C.POINTER(C.c_uint64), C.c_uint64,
+                                              C.POINTER(C.c_uint64), scp, C.POINTER(C.c_int32),
+                                              u8p, u8p, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_uint32), C.c_int]
+        L.ref_nw_first_linear_s.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, scp,
+                                            C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int),
+                                            C.c_char_p, C.c_size_t, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_uint64)]
+        L.ref_nw_score_linear_s.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, scp,
+                                            C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int)]
         L.ref_nw_first_linear.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.c_int,
                                           C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int),
                                           C.c_char_p, C.c_size_t, C.POINTER(C.c_int64),
@@ -125,11 +152,14 @@ class NwOracle:
 
 
 def nw(query: bytes, db: bytes, *, literal_dfs: bool = True, max_pops: int = 2_000_000,
-       out_cap: int = 1 << 22, max_blocks: int = 0) -> NwOracle:
+       out_cap: int = 1 << 22, max_blocks: int = 0, scoring=None) -> NwOracle:
+    """`scoring` = (match, mismatch, gap_open, gap_extend) replaces the
+    reference's four constants in the fill; None is the reference's scheme."""
     L = lib()
     q, d = _u8(query), _u8(db)
     m = _Mats()
-    if L.ref_nw_fill(q, len(query), d, len(db), C.byref(m)) != 0:
+    sc = _scoring(scoring)
+    if L.ref_nw_fill_s(q, len(query), d, len(db), C.byref(sc), C.byref(m)) != 0:
         raise MemoryError("oracle fill")
     try:
         H, W = len(db) + 1, len(query) + 1
@@ -163,19 +193,21 @@ def nw(query: bytes, db: bytes, *, literal_dfs: bool = True, max_pops: int = 2_0
         L.ref_nw_free(C.byref(m))
 
 
-def nw_score_linear(query: bytes, db: bytes, threads: int = 0) -> tuple[int, int, bool]:
+def nw_score_linear(query: bytes, db: bytes, threads: int = 0, *,
+                    scoring=None) -> tuple[int, int, bool]:
     """(score, end_states, panics) of one pair in linear memory (reflinear.c),
     for pairs too large for the full-matrix oracle (configs[3])."""
     if threads <= 0:
         threads = min(16, os.cpu_count() or 1)
     sc, es, pan = C.c_int32(0), C.c_uint8(0), C.c_int(0)
-    if lib().ref_nw_score_linear(_u8(query), len(query), _u8(db), len(db), threads,
-                                 C.byref(sc), C.byref(es), C.byref(pan)) != 0:
+    if lib().ref_nw_score_linear_s(_u8(query), len(query), _u8(db), len(db), threads,
+                                   C.byref(_scoring(scoring)), C.byref(sc), C.byref(es),
+                                   C.byref(pan)) != 0:
         raise MemoryError("oracle linear fill")
     return sc.value, es.value, bool(pan.value)
 
 
-def nw_first_linear(query: bytes, db: bytes, threads: int = 0):
+def nw_first_linear(query: bytes, db: bytes, threads: int = 0, *, scoring=None):
     """(score, end_states, panics, first_ops or None, dead_nodes) of one pair:
     the linear-memory fill keeping 1 B of parent sets per cell and the
     reference DFS's first event over them (reflinear.c), for pairs too large
@@ -187,9 +219,9 @@ def nw_first_linear(query: bytes, db: bytes, threads: int = 0):
     cap = len(query) + len(db) + 1
     ops = C.create_string_buffer(cap)
     olen, dead = C.c_int64(0), C.c_uint64(0)
-    if lib().ref_nw_first_linear(_u8(query), len(query), _u8(db), len(db), threads, C.byref(sc),
-                                 C.byref(es), C.byref(pan), ops, cap, C.byref(olen),
-                                 C.byref(dead)) != 0:
+    if lib().ref_nw_first_linear_s(_u8(query), len(query), _u8(db), len(db), threads,
+                                   C.byref(_scoring(scoring)), C.byref(sc), C.byref(es),
+                                   C.byref(pan), ops, cap, C.byref(olen), C.byref(dead)) != 0:
         raise MemoryError("oracle linear first alignment")
     first = ops.raw[:olen.value].decode() if olen.value >= 0 else None
     return sc.value, es.value, bool(pan.value), first, dead.value
@@ -265,7 +297,7 @@ class BatchCheck:
         return None if n < 0 else self.cig[int(self.cig_off[p]):int(self.cig_off[p]) + n]
 
 
-def check_pairs(qs, q_off, ds, d_off, threads: int = 0) -> BatchCheck:
+def check_pairs(qs, q_off, ds, d_off, threads: int = 0, *, scoring=None) -> BatchCheck:
     """Reference results of every pair (k-th query slice vs k-th db slice of
     the CSR inputs): literal fill + memoised DFS (refcheck.c), on threads."""
     if threads <= 0:
@@ -281,13 +313,14 @@ def check_pairs(qs, q_off, ds, d_off, threads: int = 0) -> BatchCheck:
     out = BatchCheck(np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8),
                      np.zeros(n, np.int32), co, np.zeros(max(1, int(co[-1])), np.uint32))
     P = lambda a, t: a.ctypes.data_as(C.POINTER(t))  # noqa: E731
-    rc = lib().ref_nw_check_pairs_mt(P(qs if len(qs) else np.zeros(1, np.uint8), C.c_uint8),
-                                      P(qo, C.c_uint64),
-                                      P(ds if len(ds) else np.zeros(1, np.uint8), C.c_uint8),
-                                      P(do, C.c_uint64), n, P(co, C.c_uint64),
-                                      P(out.score, C.c_int32), P(out.end_states, C.c_uint8),
-                                      P(out.panics, C.c_uint8), P(out.cig_len, C.c_int32),
-                                      P(out.cig, C.c_uint32), threads)
+    sc = _scoring(scoring)
+    rc = lib().ref_nw_check_pairs_mt_s(P(qs if len(qs) else np.zeros(1, np.uint8), C.c_uint8),
+                                        P(qo, C.c_uint64),
+                                        P(ds if len(ds) else np.zeros(1, np.uint8), C.c_uint8),
+                                        P(do, C.c_uint64), n, P(co, C.c_uint64), C.byref(sc),
+                                        P(out.score, C.c_int32), P(out.end_states, C.c_uint8),
+                                        P(out.panics, C.c_uint8), P(out.cig_len, C.c_int32),
+                                        P(out.cig, C.c_uint32), threads)
     if rc != 0:
         raise MemoryError("oracle check_pairs")
     out.panics = out.panics.astype(bool)

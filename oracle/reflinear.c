@@ -31,11 +31,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#define GO (-8)
-#define GE (-6)
-#define MIS (-4)
-#define MAT 5
-
 typedef struct {
     int32_t m, i, d;
     uint8_t f; /* bit0 M, bit1 I, bit2 D: panic reachable */
@@ -50,6 +45,7 @@ typedef struct {
     _Atomic size_t *prog;   /* prog[t]: rows of col[t] published */
     lin_cell end;           /* (ld, lq) */
     uint8_t *codes;         /* optional: parent sets per cell, row-major (ld+1) x (lq+1) */
+    ref_nw_scoring sc;
 } lin_job;
 
 typedef struct {
@@ -60,7 +56,7 @@ typedef struct {
 static inline int32_t mx2(int32_t a, int32_t b) { return a > b ? a : b; }
 
 /* column 0 at row i (:200-216), origin (:172-182) */
-static lin_cell col0(size_t i) {
+static lin_cell col0(size_t i, const ref_nw_scoring *sc) {
     lin_cell c;
     if (i == 0) {
         c.m = 0;
@@ -69,7 +65,7 @@ static lin_cell col0(size_t i) {
         c.f = 0;
     } else {
         c.m = REF_SENTINEL;
-        c.i = GO + ((int32_t)i + 1) * GE;
+        c.i = sc->gap_open + ((int32_t)i + 1) * sc->gap_extend;
         c.d = REF_SENTINEL;
         c.f = 2; /* I[i>=1][0] is itself a panic node */
     }
@@ -80,6 +76,8 @@ static void *lin_stripe(void *vp) {
     lin_arg *a = (lin_arg *)vp;
     lin_job *J = a->job;
     const int t = a->t;
+    const int32_t MAT = J->sc.match, MIS = J->sc.mismatch, GO = J->sc.gap_open,
+                  GE = J->sc.gap_extend;
     const size_t c0 = 1 + (size_t)t * J->w;
     size_t c1 = c0 + J->w;
     if (c1 > J->lq + 1) c1 = J->lq + 1;
@@ -94,7 +92,7 @@ static void *lin_stripe(void *vp) {
         while ((avail = atomic_load_explicit(&J->prog[t], memory_order_acquire)) < 1) sched_yield();
         prev[0] = left[0];
     } else {
-        prev[0] = col0(0);
+        prev[0] = col0(0, &J->sc);
     }
     for (size_t k = 0; k < n; ++k) {
         const size_t j = c0 + k;
@@ -115,7 +113,7 @@ static void *lin_stripe(void *vp) {
             }
             cur[0] = left[i];
         } else {
-            cur[0] = col0(i);
+            cur[0] = col0(i, &J->sc);
         }
         const uint8_t di = J->d[i - 1];
         for (size_t k = 1; k <= n; ++k) {
@@ -166,7 +164,8 @@ static void *lin_stripe(void *vp) {
 }
 
 static int lin_run(lin_job *Jp, const uint8_t *q, size_t lq, const uint8_t *d, size_t ld,
-                   int threads, uint8_t *codes, int32_t *score, uint8_t *end_states, int *panics) {
+                   int threads, const ref_nw_scoring *sc, uint8_t *codes, int32_t *score,
+                   uint8_t *end_states, int *panics) {
     lin_job J;
     memset(&J, 0, sizeof(J));
     J.q = q;
@@ -174,6 +173,7 @@ static int lin_run(lin_job *Jp, const uint8_t *q, size_t lq, const uint8_t *d, s
     J.lq = lq;
     J.ld = ld;
     J.codes = codes;
+    J.sc = *sc;
     if (codes) { /* boundary parent sets (:183-216): D[0][j] <- D[0][j-1], I[i][0] <- I[i-1][0] */
         codes[0] = 0;
         for (size_t j = 1; j <= lq; ++j) codes[j] = 32;
@@ -187,7 +187,7 @@ static int lin_run(lin_job *Jp, const uint8_t *q, size_t lq, const uint8_t *d, s
     J.w = w;
     lin_cell end;
     if (lq == 0) {
-        end = col0(ld);
+        end = col0(ld, &J.sc);
     } else {
         J.col = (lin_cell **)calloc((size_t)nt, sizeof(lin_cell *));
         J.prog = (_Atomic size_t *)calloc((size_t)nt + 1, sizeof(_Atomic size_t));
@@ -227,7 +227,14 @@ static int lin_run(lin_job *Jp, const uint8_t *q, size_t lq, const uint8_t *d, s
 
 int ref_nw_score_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
                         int32_t *score, uint8_t *end_states, int *panics) {
-    return lin_run(NULL, q, lq, d, ld, threads, NULL, score, end_states, panics);
+    return ref_nw_score_linear_s(q, lq, d, ld, threads, &ref_nw_default_scoring, score, end_states,
+                                 panics);
+}
+
+int ref_nw_score_linear_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
+                          const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                          int *panics) {
+    return lin_run(NULL, q, lq, d, ld, threads, sc, NULL, score, end_states, panics);
 }
 
 /* ---- the reference DFS over stored parent sets, first event only ---- */
@@ -259,6 +266,14 @@ static int lin_parents(const uint8_t *codes, size_t W, int st, size_t x, size_t 
 int ref_nw_first_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
                         int32_t *score, uint8_t *end_states, int *panics, char *ops,
                         size_t ops_cap, int64_t *ops_len, uint64_t *dead_nodes) {
+    return ref_nw_first_linear_s(q, lq, d, ld, threads, &ref_nw_default_scoring, score,
+                                 end_states, panics, ops, ops_cap, ops_len, dead_nodes);
+}
+
+int ref_nw_first_linear_s(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld, int threads,
+                          const ref_nw_scoring *sc, int32_t *score, uint8_t *end_states,
+                          int *panics, char *ops, size_t ops_cap, int64_t *ops_len,
+                          uint64_t *dead_nodes) {
     const size_t W = lq + 1, n = (ld + 1) * W;
     uint8_t *codes = (uint8_t *)malloc(n);
     uint8_t *dead = (uint8_t *)calloc(n, 1); /* bit st: (cell, st) explored, no terminal */
@@ -269,7 +284,7 @@ int ref_nw_first_linear(const uint8_t *q, size_t lq, const uint8_t *d, size_t ld
         free(stk);
         return -1;
     }
-    int rc = lin_run(NULL, q, lq, d, ld, threads, codes, score, end_states, panics);
+    int rc = lin_run(NULL, q, lq, d, ld, threads, sc, codes, score, end_states, panics);
     *ops_len = -1;
     uint64_t ndead = 0;
     if (rc == 0) {

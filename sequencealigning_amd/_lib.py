@@ -52,6 +52,12 @@ class NwScoring(C.Structure):
                 ("gap_extend", C.c_int32)]
 
 
+class NwPairPath(C.Structure):
+    """saln_nw_pair_path: what execute does with one pair of a plan."""
+    _fields_ = [("variant", C.c_int32), ("packed", C.c_int32), ("rebase", C.c_int32),
+                ("table", C.c_int32), ("stripe_pk", C.c_int32), ("rows_k", C.c_int32)]
+
+
 class NwResult(C.Structure):
     _fields_ = [("score", C.c_int32), ("status", C.c_int32), ("cigar_len", C.c_uint32),
                 ("end_states", C.c_uint8), ("printed", C.c_uint8), ("flags", C.c_uint8),
@@ -84,7 +90,7 @@ EXPORTS = [
     "saln_context_create", "saln_context_destroy", "saln_last_error", "saln_abi_version",
     "saln_nw_align", "saln_nw_render", "saln_nw_dense_mask", "saln_nw_align_batch",
     "saln_nw_plan_create", "saln_nw_plan_create_full", "saln_nw_plan_dense_mask",
-    "saln_nw_plan_walk_codes",
+    "saln_nw_plan_walk_codes", "saln_nw_plan_pair_path",
     "saln_nw_plan_info", "saln_nw_cigar_offsets", "saln_nw_execute",
     "saln_nw_plan_set_timing", "saln_nw_plan_kernel_time", "saln_nw_plan_set_async",
     "saln_nw_plan_set_score_only", "saln_nw_plan_sync", "saln_nw_plan_destroy",
@@ -169,6 +175,7 @@ def lib() -> C.CDLL:
         L.saln_nw_plan_create_full.argtypes = L.saln_nw_plan_create.argtypes
         L.saln_nw_plan_dense_mask.argtypes = [vp, C.c_uint64, vp]
         L.saln_nw_plan_walk_codes.argtypes = [vp, C.c_uint64, vp]
+        L.saln_nw_plan_pair_path.argtypes = [vp, C.c_uint64, C.POINTER(NwPairPath)]
         L.saln_nw_plan_info.argtypes = [vp, u64p, u64p, u64p]
         L.saln_nw_cigar_offsets.argtypes = [vp, vp]
         L.saln_nw_execute.argtypes = [vp, vp, vp, vp, vp, vp]

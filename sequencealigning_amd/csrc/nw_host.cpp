@@ -73,6 +73,9 @@ struct saln_nw_plan {
     int stripe_rows = 0;     // else: row fill with this many columns per lane (0 = skewed fill)
     uint32_t stripe_sub = kStripeSubMax;  // boundary columns per 256-column chunk
     int stripe_layout() const { return stripe_pk ? 1 : stripe_rows ? 2 : 0; }
+    // launch_fill's code format for variant v and whether its launch has a bail word
+    int fill_codes(int v) const { return score_only ? 2 : full_codes ? 1 : nib[v] ? 3 : 0; }
+    bool has_bail() const { return d_bail[async_tb ? buf : 0] != nullptr; }
     bool full_codes = false;  // walk codes (default) or every parent set (decided at creation)
     bool nib[kNumVariants] = {};  // variant stores 4-bit walk codes (Geom::LBn segments)
     bool score_only = false;  // no parent codes / traceback (saln_nw_plan_set_score_only)
@@ -781,8 +784,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
         fx.bail = p->d_bail[cur] ? p->d_bail[cur] + v : nullptr;
         HIP_TRY(launch_fill(v, p->d_pairs, a, b - a, d_q, d_db, mask, p->d_scratch, endh,
                             d_results, d_cigar, p->sc,
-                            p->score_only ? 2 : p->full_codes ? 1 : p->nib[v] ? 3 : 0,
-                            p->var_maxld[v], s, fx));
+                            p->fill_codes(v), p->var_maxld[v], s, fx));
     }
     // the fill's end (timed: its timing event doubles as the hand-off)
     hipEvent_t filled = ev ? ev[1] : p->sync_ev[0];
@@ -832,6 +834,26 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
         if (t != s) HIP_TRY(hipStreamWaitEvent(s, p->tb_done(cur), 0));
         p->tb_pending[cur] = false;
     }
+    return SALN_OK;
+}
+
+int saln_nw_plan_pair_path(const saln_nw_plan *p, uint64_t pair, saln_nw_pair_path *out) {
+    if (!p || !out || pair >= p->n_pairs) return SALN_E_INVALID;
+    const NwPairDesc &d = p->h_pairs[p->plan_index[pair]];
+    *out = saln_nw_pair_path{-1, 0, 0, 0, 0, 0};
+    if (!d.len_q || !d.len_db) return SALN_OK;
+    const int v = (int)d.variant;
+    out->variant = v;
+    if (v == kStripeVariant) {
+        out->stripe_pk = p->stripe_pk;
+        out->packed = p->stripe_pk;
+        out->rows_k = p->stripe_rows;
+        return SALN_OK;
+    }
+    const FillPath fp = fill_path(v, p->fill_codes(v), p->var_maxld[v], p->sc, p->opts, p->has_bail());
+    out->packed = fp.packed;
+    out->rebase = fp.rebase;
+    out->table = fp.table;
     return SALN_OK;
 }
 

@@ -98,6 +98,16 @@ struct FillExtras {
     uint32_t epoch = 0;
     std::vector<std::function<hipError_t(hipStream_t)>> *deferred = nullptr;
 };
+// What launch_fill does with a variant's pairs (saln_nw_plan_pair_path reports
+// it): packed int16 halves or i32 lanes; for packed launches the rebasing
+// frame (the longest db leaves the single int16 frame) and the body: 0
+// generic, 2 / 4 the table body at that scale, 3 row profiles.
+struct FillPath {
+    bool packed = false, rebase = false;
+    int table = 0;
+};
+FillPath fill_path(int variant, int codes, uint32_t ld_max, const Scoring &sc, const Options &o,
+                   bool have_bail);
 hipError_t launch_fill(int variant, const NwPairDesc *pairs, uint32_t first, uint32_t count,
                        const uint8_t *qs, const uint8_t *ds, uint8_t *mask, int2 *scratch,
                        int32_t *end_h, saln_nw_result *results, uint32_t *cigar, Scoring sc,

@@ -3239,6 +3239,7 @@ constexpr uint32_t kFillG[kNumVariants] = {16, 16, 64, 64, 8, 16, 32, 16, 64};
 constexpr size_t kPackedLdsMax = 80 * 1024;
 constexpr size_t kLdsPerCu = 160 * 1024;  // MI355X_MICROARCH.md
 static bool packed_ok(uint32_t lq, uint32_t ld, const Scoring &sc);
+static bool packed_single_ok(uint32_t G, uint32_t W, uint32_t ld, const Scoring &sc);
 
 template <int G, int K>
 static void fill_i32(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uint32_t first,
@@ -3289,12 +3290,45 @@ static bool pk_free_ok(const Scoring &sc, uint32_t W, uint32_t rows, int scale =
     return lo <= kFreeBias - 0x400 && hi <= 0x7BFF - kFreeBias;
 }
 
+// The body a packed plan launch of G x K lane groups runs (FillPath::table):
+// the table body where the launch stores 4-bit walk codes, or full parent
+// sets in 16-lane groups, nw.pk_tab is on, the workspace has a bail word, the
+// extension-free frame holds `ld_max` rows (pk_free_ok) and the 32-bit staged
+// rows fit the LDS; else the generic body.  nw.pk_tab 1: scale 2; 2: the
+// scale-4 body where its window holds the launch, else scale 2; 3: row
+// profiles (scale 2).  Full parent sets: row profiles.
+static int pk_table_body(uint32_t G, uint32_t K, int codes, uint32_t ld_max, bool rebase,
+                         const Scoring &sc, const Options &o, bool have_bail) {
+    if (codes != kCodesNib && !(codes == kCodesFull && G == 16)) return 0;
+    // (the table body stages 32-bit row words; a rebasing fallback 16-bit ones)
+    // (and keeps four workgroups per CU where the rebasing fill had them)
+    const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G) * (rebase ? 2 : 4);
+    const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
+    if (!o[Opt::PkTab] || !have_bail || !pk_free_ok(sc, G * K, ld_max) ||
+        lds_tab > std::max(lds, kLdsPerCu / 4))
+        return 0;
+    if (codes == kCodesFull) return 3;
+    return o[Opt::PkTab] == 2 && pk_free_ok(sc, G * K, ld_max, 4) ? 4 : o[Opt::PkTab] == 3 ? 3 : 2;
+}
+
+FillPath fill_path(int variant, int codes, uint32_t ld_max, const Scoring &sc, const Options &o,
+                   bool have_bail) {
+    FillPath fp;
+    fp.packed = kPacked[variant];
+    if (!fp.packed) return fp;
+    // packed pairs beyond one int16 frame (packed_ok_rebase) take the rebasing fill
+    fp.rebase = !packed_single_ok(kVariants[variant].G, kVariants[variant].W(), ld_max, sc);
+    fp.table = pk_table_body(kVariants[variant].G, kVariants[variant].K, codes, ld_max, fp.rebase,
+                             sc, o, have_bail);
+    return fp;
+}
+
 template <int G, int K, int KS = K>
 static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uint32_t first,
                           uint32_t count, const uint8_t *qs, const uint8_t *ds, uint8_t *mask,
                           int32_t *end_h, saln_nw_result *, uint32_t *, Scoring sc,
-                          int codes, uint32_t ld_max, bool rebase, const FillExtras &fx) {
-    const Options &o = *fx.o;
+                          int codes, uint32_t ld_max, const FillPath &fp, const FillExtras &fx) {
+    const bool rebase = fp.rebase;
     const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G) * (rebase ? 2 : 4);
     if (lds > kPackedLdsMax) return hipErrorInvalidValue;  // choose_variant keeps ld below this
     const PlanSrc src{pairs, first, end_h};
@@ -3311,17 +3345,11 @@ static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uin
         const auto kern = nw_fill_pk_kernel<G, K, decltype(codes_c)::value, PlanSrc, KS,
                                             decltype(rebase_c)::value>;
         if constexpr (decltype(codes_c)::value == kCodesNib && KS == K) {
-            // (the table body stages 32-bit row words; a rebasing fallback 16-bit ones)
-            // (and keeps four workgroups per CU where the rebasing fill had them)
             const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
-            if (o[Opt::PkTab] && fx.bail && pk_free_ok(sc, G * K, ld_max) &&
-                lds_tab <= std::max(lds, kLdsPerCu / 4)) {
+            if (fp.table) {
                 constexpr bool kRb = decltype(rebase_c)::value;
-                // nw.pk_tab 1: scale 2; 2: the scale-4 body where its window
-                // holds the launch, else scale 2; 3: row profiles (scale 2)
                 const size_t lds_prof = lds_tab;
-                const int sel = o[Opt::PkTab] == 2 && pk_free_ok(sc, G * K, ld_max, 4) ? 4
-                                : o[Opt::PkTab] == 3 ? 3 : 2;
+                const int sel = fp.table;  // pk_table_body
                 const void *tk = sel == 4 ? (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 4>
                                  : sel == 3 ? (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 3>
                                             : (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 2>;
@@ -3354,8 +3382,7 @@ static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uin
         // 16-lane geometries (queries of up to 256 columns), nw.pk_tab != 0
         if constexpr (decltype(codes_c)::value == kCodesFull && KS == K && G == 16) {
             const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
-            if (o[Opt::PkTab] && fx.bail && pk_free_ok(sc, G * K, ld_max) &&
-                lds_tab <= std::max(lds, kLdsPerCu / 4)) {
+            if (fp.table) {
                 constexpr bool kRb = decltype(rebase_c)::value;
                 const void *tk = (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 3, kCodesFull>;
                 const void *fk = (const void *)nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb, kCodesFull>;
@@ -3438,7 +3465,7 @@ static hipError_t avsa_pk(const AvsaSrc &src, uint32_t count, const uint8_t *qs,
     const uint64_t blocks = avsa_blocks(G, count);
     if (blocks * 256 > 0xFFFFFFFFull) return hipErrorInvalidConfiguration;  // 32-bit grid
     const dim3 grid((uint32_t)blocks);
-    const bool rebase = !packed_ok(G * K, ld_max, sc);
+    const bool rebase = !packed_single_ok(G, G * K, ld_max, sc);
     const size_t lds = (size_t)gpb * (ld_max + 2 * G) * (rebase ? 2 : 4);
     if (lds > kPackedLdsMax) return hipErrorInvalidValue;
     // the table body stages 32-bit row words, the rebasing xor body 16-bit ones
@@ -3584,19 +3611,18 @@ hipError_t launch_fill(int variant, const NwPairDesc *pairs, uint32_t first, uin
     const uint32_t groups = kPacked[variant] ? (count + 1) / 2 : count;
     const uint32_t sup = 8 * blocks_per_pack(kPacked[variant] ? 2 * gpb : gpb);
     const dim3 grid(((groups + gpb - 1) / gpb + sup - 1) / sup * sup);
-    // packed pairs beyond one int16 frame (packed_ok_rebase) take the rebasing fill
-    const bool rebase = kPacked[variant] && !packed_ok(kVariants[variant].W(), ld_max, sc);
+    const FillPath fp = fill_path(variant, codes, ld_max, sc, *fx.o, fx.bail != nullptr);
     hipError_t e = hipSuccess;
     switch (variant) {
         case 0: fill_i32<16, 10>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
         case 1: fill_i32<16, 16>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
         case 2: fill_i32<64, 8>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
         case 3: return hipErrorInvalidValue;  // stripes: launch_fill_stripes
-        case 4: e = fill_pk<8, 19>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, rebase, fx); break;
-        case 5: e = fill_pk<16, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, rebase, fx); break;
-        case 7: e = fill_pk<16, 10>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, rebase, fx); break;
-        case 8: e = fill_pk<64, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, rebase, fx); break;
-        default: e = fill_pk<32, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, rebase, fx); break;
+        case 4: e = fill_pk<8, 19>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
+        case 5: e = fill_pk<16, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
+        case 7: e = fill_pk<16, 10>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
+        case 8: e = fill_pk<64, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
+        default: e = fill_pk<32, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
     }
     if (e != hipSuccess) return e;
     return hipGetLastError();
@@ -4022,6 +4048,15 @@ static bool packed_range_ok(uint32_t lq, uint32_t rows, const Scoring &sc) {
 static bool packed_ok(uint32_t lq, uint32_t ld, const Scoring &sc) {
     return packed_range_ok(lq, ld, sc);
 }
+// One int16 frame holds a launch of G-lane groups of W columns whose longest
+// db has `ld` rows: the values of all W columns (a launch decides its frame
+// from the group's width, not from a pair's own query) and the 32-bit staged
+// db rows (kPackedLdsMax; under small penalties the value range alone admits
+// more rows than the LDS holds).  choose_variant and the launches share it, so
+// a pair is never handed to a frame that no guard accepted for it.
+static bool packed_single_ok(uint32_t G, uint32_t W, uint32_t ld, const Scoring &sc) {
+    return packed_ok(W, ld, sc) && (size_t)(256 / G) * (ld + 2 * G) * 4 <= kPackedLdsMax;
+}
 // The rebasing fill (kRebase).  At step t a lane's value is
 // X~(r,c) - drift * r0 with r in [r0 - G, r0 + kRebaseSteps) and
 //   X~(r,c) - drift*r0 = [X~(r,c) - X~(r,0)] + [X~(r,0) - drift*r] + drift*(r - r0):
@@ -4056,12 +4091,17 @@ int choose_variant(uint32_t len_q, uint32_t len_db, const Scoring &sc, bool narr
     // int16 frame or the rebasing one (launch_fill decides from the widest)
     if (narrow && len_q <= 152) {
         const Geom g = kVariants[4];
-        if (packed_ok(g.W(), len_db, sc) || packed_ok_rebase(len_q, len_db, sc, g.G, g.W())) return 4;
+        if (packed_single_ok(g.G, g.W(), len_db, sc) ||
+            packed_ok_rebase(len_q, len_db, sc, g.G, g.W()))
+            return 4;
     }
-    if (packed_ok(len_q, len_db, sc)) {
-        if (len_q <= 160) return 7;
-        if (len_q <= 256) return 5;
-        if (len_q <= 512) return 6;
+    // one int16 frame, judged as the launch judges it: over the whole width of
+    // the variant's lane groups (a query narrower than its group once passed
+    // here on its own width, and the launch then took the rebasing frame for
+    // it without packed_ok_rebase having been asked)
+    if (len_q <= 512) {
+        const int v = len_q <= 160 ? 7 : len_q <= 256 ? 5 : 6;
+        if (packed_single_ok(kVariants[v].G, kVariants[v].W(), len_db, sc)) return v;
     }
     // longer db: the same packed variants with a rebasing int16 frame; 513 to
     // 1,024 query columns in 64-lane groups (narrower queries would leave

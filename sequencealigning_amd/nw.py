@@ -263,6 +263,16 @@ def nw_align_batch(queries, dbs, pairs=None, mode: Mode = Mode.Global, *, scorin
     return res, cigars
 
 
+@dataclass(frozen=True)
+class PairPath:
+    variant: int      # fill variant number; -1: a pair with an empty side
+    packed: bool      # int16 halves (two pairs per lane group) or i32 lanes
+    rebase: bool      # the packed launch uses the rebasing int16 frame
+    table: int        # packed launch body: 0 generic, 2 / 4 table at that scale, 3 row profiles
+    stripe_pk: bool   # column-stripe pairs: packed stripes
+    rows_k: int       # column-stripe pairs: the row fill's columns per lane
+
+
 class NwPlan:
     """Device-resident batch: plan once from host lengths, execute on torch
     device tensors (inputs resident in HBM).  Used by bench.py and the
@@ -332,6 +342,16 @@ class NwPlan:
         _lib.check(self._L.saln_nw_plan_walk_codes(self._h, pair, out.ctypes.data_as(C.c_void_p)),
                    "saln_nw_plan_walk_codes")
         return out
+
+    def pair_path(self, pair: int) -> "PairPath":
+        """What the next execute does with pair `pair` (test introspection,
+        saln_nw_plan_pair_path): the fill variant and, from the code that
+        launches it, the frame and body of its launch."""
+        pp = _lib.NwPairPath()
+        _lib.check(self._L.saln_nw_plan_pair_path(self._h, pair, C.byref(pp)),
+                   "saln_nw_plan_pair_path")
+        return PairPath(pp.variant, bool(pp.packed), bool(pp.rebase), pp.table,
+                        bool(pp.stripe_pk), pp.rows_k)
 
     def status(self) -> int:
         """Wait for every execute since the last call; return and clear the

@@ -81,3 +81,13 @@ def test_status_codes_match_header():
     from sequencealigning_amd import _lib
     assert re.search(r"SALN_E_DEVICE_WAIT = (-\d+)", src).group(1) == str(_lib.E_DEVICE_WAIT)
     assert re.search(r"SALN_FLAG_WAIT_TIMEOUT (\d+)u", src).group(1) == str(_lib.FLAG_WAIT_TIMEOUT)
+
+
+def test_pair_path_rejects_null_arguments(saln):
+    """saln_nw_plan_pair_path is plan introspection: without a plan or an
+    output record it is an argument error (no device needed)."""
+    from sequencealigning_amd import _lib
+    L = _lib.lib()
+    out = _lib.NwPairPath()
+    assert ctypes.sizeof(_lib.NwPairPath) == 24
+    assert L.saln_nw_plan_pair_path(None, 0, ctypes.byref(out)) == _lib.E_INVALID

@@ -236,7 +236,8 @@ def test_table_fill_equals_generic(saln, oracle, saln_opt, case, tab):
     extension-free frame, and its fallback launch for the waves whose pairs
     hold a byte other than A, C, G, T) equals nw.pk_tab = 0 on 20,000
     configs[1]-shaped pairs: every result field and every CIGAR word.  "acgt"
-    is also checked against the oracle pair by pair; "with_n" puts an N into
+    and "scheme" are also checked against the oracle (with the same scheme)
+    pair by pair; "with_n" puts an N into
     1 % of the queries and 1 % of the dbs (those waves take the fallback
     launch, the rest of the launch the table body); "scheme" uses
     {2, -3, -5, -2} (bonuses 12 / 2).  "long_db" / "long_db_n": 150 x 500
@@ -272,8 +273,8 @@ def test_table_fill_equals_generic(saln, oracle, saln_opt, case, tab):
     r0, c0, o0 = _run_plan(saln, qs, qo, ds, do, scoring)
     assert np.array_equal(r1, r0)
     assert np.array_equal(o1, o0) and np.array_equal(c1, c0)
-    if case in ("acgt", "long_db"):
-        want = oracle.check_pairs(qs, qo, ds, do)
+    if case in ("acgt", "long_db", "scheme"):
+        want = oracle.check_pairs(qs, qo, ds, do, scoring=scoring)
         assert np.array_equal(r1["score"], want.score)
         assert np.array_equal(r1["end_states"], want.end_states)
         assert np.array_equal(r1["status"] == saln._lib.REF_PANIC_BOUNDARY, want.panics)

@@ -144,8 +144,25 @@ def test_span_relay_wait_limit_bounds_each_row():
     a.set_wait_limit(1 << 17)
     vals = torch.arange(1, R + 1, dtype=torch.int64, device="cuda") * 3 + 7
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    _lib.check(_lib.lib().saln_nw_span_forward(a._h, b._h, 1, R, side.cuda_stream),
+    # the relay polls on a CU-masked stream over every CU, as SpanChain's edge
+    # streams do: such a stream has a hardware queue of its own.  On a plain
+    # stream the relay can share one of the process's few hardware queues with
+    # the writer, whose copies then queue behind the polling kernel until every
+    # wait has run out (which streams share depends on those created before:
+    # the test then passed or failed with the tests that ran ahead of it)
+    import ctypes as C
+    L, ctx = _lib.lib(), _lib.context(0)
+    n_cu = C.c_uint32()
+    _lib.check(L.saln_device_cu_count(ctx, C.byref(n_cu)), "saln_device_cu_count")
+    nw = (n_cu.value + 31) // 32
+    words = [0xFFFFFFFF] * nw
+    if n_cu.value % 32:
+        words[-1] = (1 << (n_cu.value % 32)) - 1
+    h_side = C.c_void_p()
+    _lib.check(L.saln_stream_create_cu_mask(ctx, (C.c_uint32 * nw)(*words), nw, C.byref(h_side)),
+               "saln_stream_create_cu_mask")
+    side = torch.cuda.ExternalStream(h_side.value)
+    _lib.check(L.saln_nw_span_forward(a._h, b._h, 1, R, side.cuda_stream),
                "saln_nw_span_forward")
     # the writes go on a stream of their own (the null stream could wait for
     # the relay), and nothing here synchronizes the device before they are in
@@ -162,6 +179,7 @@ def test_span_relay_wait_limit_bounds_each_row():
     assert torch.equal(b.inbox[1:R + 1], vals)
     a.close()
     b.close()
+    L.saln_stream_destroy(ctx, h_side)
 
 
 def _relay_worker(rank, world, port, q, d, out):
@@ -279,19 +297,28 @@ def test_span_chain_very_long_linear_oracle(shape, n):
 @pytest.mark.parametrize("scoring", [(2, -3, -5, -2), (5, -4, -8, -20), (1, -1, -2, -1)])
 def test_span_chain_custom_scoring_matches_plan(scoring):
     """Other scoring schemes through the spans equal the single-GPU plan's
-    result word for word, incl. gap penalties large enough that the
+    result word for word, and the plan's equals the linear-memory oracle's
+    under the same scheme, incl. gap penalties large enough that the
     boundary row / column fall to the reference's -32768 sentinel inside a
     4 kbp pair (dead-end end states, nothing printed)."""
     import sequencealigning_amd as saln
     from nw_check import rand_seq
+    from oracle import refcpu
 
+    from sequencealigning_amd.nw import cigar_ops_string
     from sequencealigning_amd.span import nw_align_long_spans
     rng = np.random.default_rng(45)
     q = rand_seq(rng, 4000)
     for d in (_mut(rng, q, 0.05), rand_seq(rng, 3500)):
+        want = saln.n_w_align(q, d, scoring=scoring)
+        sc, es, pan, first, _ = refcpu.nw_first_linear(q, d, scoring=scoring)
+        assert (want.score, want.end_states, want.panics, want.printed) == \
+            (sc, es, pan, first is not None)
+        if first is not None:
+            assert cigar_ops_string(want.cigar) == first
         for n in (2, 5):
             r = nw_align_long_spans(q, d, n, scoring=scoring, band_rows=512)
-            _same(r, saln.n_w_align(q, d, scoring=scoring))
+            _same(r, want)
 
 
 def test_cu_range_streams_cover_every_xcd():
