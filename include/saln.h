@@ -44,6 +44,10 @@ typedef enum {
     SALN_ENUM_CAP = 6,           /* NW co-optimal enumeration hit the caller's cap */
     SALN_SPAN_UNLINKED = 7,      /* saln_nw_spans_walk only: the speculative passes did not
                                     link; walk span by span (saln_nw_span_walk) */
+    SALN_TRACE_CAP = 8,          /* saln_wfa_affine_align_batch: the pair's trace codes alone
+                                    exceed trace_budget_bytes; score only, no CIGAR */
+    SALN_INTERNAL = 9,           /* saln_wfa_affine_align_batch: the trace pass disagreed with
+                                    the score pass (internal inconsistency; never expected) */
 
     SALN_E_INVALID = -1,   /* bad argument */
     SALN_E_HIP = -2,       /* HIP runtime error (message: saln_last_error) */
@@ -581,6 +585,55 @@ int saln_wfa_affine_plan_create(saln_context *ctx, const uint64_t *q_off, uint64
 int saln_wfa_affine_execute(saln_wfa_affine_plan *plan, const uint8_t *d_q_seq,
                             const uint8_t *d_db_seq, int32_t *d_scores, void *stream);
 int saln_wfa_affine_plan_destroy(saln_wfa_affine_plan *plan);
+
+/* Alignment mode: the minimum penalty as above and one optimal alignment per
+ * pair as CIGAR words ((run << 4) | op with SALN_CIGAR_EQ/X/I/D, forward
+ * order, db as the reference sequence, like the NW paths).  Orientation: a
+ * column of '-' against a db base (the WFA's I component, which advances the
+ * db offset) is SALN_CIGAR_D; a query base against '-' (its D component) is
+ * SALN_CIGAR_I.  Among co-optimal alignments the choice is fixed (M prefers
+ * a mismatch, then the db-advancing gap, then the query-advancing gap; a gap
+ * prefers extend over open), so a pair's words do not depend on the batch,
+ * the chunk or the run. */
+typedef struct {
+    int32_t score;      /* as saln_wfa_affine_batch: the penalty, -1 or -2 */
+    int32_t status;     /* SALN_OK | SALN_TRACE_CAP | SALN_INTERNAL */
+    uint32_t cigar_len; /* CIGAR words (0: negative score, SALN_TRACE_CAP, or both sequences empty) */
+    uint32_t reserved;
+} saln_wfa_affine_result;   /* 16 bytes */
+
+/* Same pair conventions and argument errors as saln_wfa_affine_batch.  Runs
+ * the score passes, reads the scores back, then the trace fill and the walk
+ * in chunks: pairs are packed greedily in pair order into chunks of at most
+ * trace_budget_bytes of trace codes (saln_wfa_affine_trace_bytes each; 0
+ * selects 1 GiB).  A pair with score -1 or -2 has status SALN_OK and no
+ * words; a pair whose codes alone exceed the budget has its score, status
+ * SALN_TRACE_CAP and no words.  A sequence longer than 2^28-1 bases is
+ * refused.  The handle owns the words. */
+typedef struct saln_wfa_affine_aln saln_wfa_affine_aln;
+int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                uint64_t n_pairs, const saln_wfa_penalties *pen,
+                                int32_t max_score, uint64_t trace_budget_bytes,
+                                saln_wfa_affine_aln **out);
+uint64_t saln_wfa_affine_aln_count(const saln_wfa_affine_aln *a);
+/* res and cigar are optional.  cigar points into the handle, res->cigar_len
+ * words, valid until saln_wfa_affine_aln_free; the words of consecutive pairs
+ * are contiguous, in pair order. */
+int saln_wfa_affine_aln_get(const saln_wfa_affine_aln *a, uint64_t pair,
+                            saln_wfa_affine_result *res, const uint32_t **cigar);
+void saln_wfa_affine_aln_free(saln_wfa_affine_aln *a);
+/* Host only (no device needed): bytes of trace workspace of one pair with
+ * this penalty (score >= 0), the one place the layout's size is computed:
+ *   T = score / g (g = gcd(x, o+e, e)) steps;
+ *   wt = the smallest power of two >= max(64, min(2*max(0,(score-o)/e) + 1,
+ *        len_q + len_db + 1) + 2) diagonals per code row, 4 bits each;
+ *   bytes = T * wt / 2 (codes) + T rounded up to 16 (the walk's op bytes);
+ * 0 when a sequence is empty.  SALN_E_INVALID for a negative score or bad
+ * penalties. */
+int saln_wfa_affine_trace_bytes(const saln_wfa_penalties *pen, uint64_t len_q, uint64_t len_db,
+                                int32_t score, uint64_t *bytes);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

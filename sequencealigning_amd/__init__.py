@@ -14,6 +14,7 @@ from .nw import (NwAlignment, NwAllVsAll, NwPlan, alignment_rows, cigar_ops_stri
 from . import wfa
 from .wfa import WfaAlignment, WfaPlan, wfa_align, wfa_align_batch
 from . import wfa_affine
+from .wfa_affine import wfa_affine_align, wfa_affine_align_batch
 from ._lib import get_option, option_names, options, set_option
 
 __all__ = [
@@ -21,5 +22,6 @@ __all__ = [
     "Records", "parse_fasta", "parse_fasta_bytes", "NwAlignment", "NwPlan", "alignment_rows",
     "cigar_ops_string", "dense_mask", "n_w_align", "NwAllVsAll", "nw_score_all_vs_all", "nw_align_batch", "pack_csr", "render", "render_batch",
     "wfa", "WfaAlignment", "WfaPlan", "wfa_align", "wfa_align_batch", "wfa_affine",
+    "wfa_affine_align", "wfa_affine_align_batch",
     "get_option", "option_names", "options", "set_option",
 ]

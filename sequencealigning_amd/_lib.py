@@ -25,6 +25,8 @@ REF_PANIC_SLICE = 4
 NONCONVERGED = 5
 ENUM_CAP = 6
 SPAN_UNLINKED = 7
+TRACE_CAP = 8
+INTERNAL = 9
 E_INVALID = -1
 E_HIP = -2
 E_NO_DEVICE = -3
@@ -39,7 +41,8 @@ FLAG_SPEC_UNLINKED = 2  # SALN_FLAG_SPEC_UNLINKED
 STATUS_NAMES = {
     OK: "OK", NOT_IMPLEMENTED: "NOT_IMPLEMENTED", REF_PANIC_BOUNDARY: "REF_PANIC_BOUNDARY",
     REF_PANIC_TRIM: "REF_PANIC_TRIM", REF_PANIC_SLICE: "REF_PANIC_SLICE",
-    NONCONVERGED: "NONCONVERGED", ENUM_CAP: "ENUM_CAP", SPAN_UNLINKED: "SPAN_UNLINKED", E_INVALID: "E_INVALID", E_HIP: "E_HIP",
+    NONCONVERGED: "NONCONVERGED", ENUM_CAP: "ENUM_CAP", SPAN_UNLINKED: "SPAN_UNLINKED",
+    TRACE_CAP: "TRACE_CAP", INTERNAL: "INTERNAL", E_INVALID: "E_INVALID", E_HIP: "E_HIP",
     E_NO_DEVICE: "E_NO_DEVICE", E_CAPACITY: "E_CAPACITY", E_IO: "E_IO", E_FASTA: "E_FASTA",
     E_FASTA_CHARS: "E_FASTA_CHARS", E_DEVICE_WAIT: "E_DEVICE_WAIT",
 }
@@ -85,6 +88,16 @@ WFA_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("steps", "<u4"), ("aln
                     ("aln_len2", "<u4"), ("conv_offset", "<i4"), ("conv_state", "u1"),
                     ("conv_np", "u1"), ("conv_parents", "u1", (3,)), ("reserved", "u1", (3,))]
 
+
+class WfaAffineResult(C.Structure):
+    """saln_wfa_affine_result: one pair of saln_wfa_affine_align_batch."""
+    _fields_ = [("score", C.c_int32), ("status", C.c_int32), ("cigar_len", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+WFA_AFFINE_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("cigar_len", "<u4"),
+                           ("reserved", "<u4")]
+
 # symbols every build must export (tests check this list against include/saln.h)
 EXPORTS = [
     "saln_context_create", "saln_context_destroy", "saln_last_error", "saln_abi_version",
@@ -107,6 +120,8 @@ EXPORTS = [
     "saln_wfa_plan_destroy",
     "saln_wfa_affine_batch", "saln_wfa_affine_plan_create", "saln_wfa_affine_execute",
     "saln_wfa_affine_plan_destroy",
+    "saln_wfa_affine_align_batch", "saln_wfa_affine_aln_count", "saln_wfa_affine_aln_get",
+    "saln_wfa_affine_aln_free", "saln_wfa_affine_trace_bytes",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -238,6 +253,17 @@ def lib() -> C.CDLL:
                                                   C.c_int32, C.POINTER(vp)]
         L.saln_wfa_affine_execute.argtypes = [vp, vp, vp, vp, vp]
         L.saln_wfa_affine_plan_destroy.argtypes = [vp]
+        L.saln_wfa_affine_align_batch.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                                  vp, C.c_uint64, C.POINTER(WfaPenalties),
+                                                  C.c_int32, C.c_uint64, C.POINTER(vp)]
+        L.saln_wfa_affine_aln_count.argtypes = [vp]
+        L.saln_wfa_affine_aln_count.restype = C.c_uint64
+        L.saln_wfa_affine_aln_get.argtypes = [vp, C.c_uint64, C.POINTER(WfaAffineResult),
+                                              C.POINTER(u32p)]
+        L.saln_wfa_affine_aln_free.argtypes = [vp]
+        L.saln_wfa_affine_aln_free.restype = None
+        L.saln_wfa_affine_trace_bytes.argtypes = [C.POINTER(WfaPenalties), C.c_uint64,
+                                                  C.c_uint64, C.c_int32, u64p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

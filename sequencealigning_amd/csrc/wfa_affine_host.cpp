@@ -8,10 +8,16 @@
 // Two passes: every pair first runs with a W-diagonal wavefront ring; pairs
 // whose wavefront outgrows it (score -2) are compacted on the device and run
 // again with a 2x wider ring.  Score -1: the penalty exceeds max_score.
+//
+// Alignment mode (saln_wfa_affine_align_batch): the score passes, the scores
+// read back, then per chunk of at most trace_budget_bytes of trace workspace
+// the trace fill (both ring widths) and the walk of
+// wfa_affine_trace_kernels.hip; the handle owns the packed CIGAR words.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -107,7 +113,35 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
     return SALN_OK;
 }
 
+// The trace workspace of one pair (include/saln.h,
+// saln_wfa_affine_trace_bytes; the kernels' layout is in the header comment
+// of wfa_affine_trace_kernels.hip): T steps, wavefronts of at most `width`
+// diagonals, code rows of wt diagonals.
+struct TraceLayout {
+    uint64_t T = 0, width = 0, wt = 64, bytes = 0;
+};
+
+TraceLayout trace_layout(const WfaAffParams &prm, uint64_t lq, uint64_t ld, int32_t score) {
+    TraceLayout l;
+    if (lq == 0 || ld == 0) return l;  // one gap run: no codes
+    l.T = (uint64_t)(score / prm.g);
+    // a gap of n columns costs o + n e, so |k| <= (score - o) / e
+    const uint64_t reach = score > prm.o ? (uint64_t)((score - prm.o) / prm.e) : 0;
+    l.width = std::min<uint64_t>(2 * reach + 1, lq + ld + 1);
+    while (l.wt < l.width + 2) l.wt <<= 1;
+    l.bytes = l.T * (l.wt / 2) + ((l.T + 15) & ~15ull);
+    return l;
+}
+
 }  // namespace
+
+// The result handle of saln_wfa_affine_align_batch: pair k's words are
+// words[off[k] .. off[k] + res[k].cigar_len).
+struct saln_wfa_affine_aln {
+    std::vector<saln_wfa_affine_result> res;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> words;
+};
 
 extern "C" {
 
@@ -237,5 +271,190 @@ int saln_wfa_affine_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_
     TRY(hipMemcpy(scores, dsc, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
     return SALN_OK;
 }
+
+int saln_wfa_affine_trace_bytes(const saln_wfa_penalties *pen, uint64_t len_q, uint64_t len_db,
+                                int32_t score, uint64_t *bytes) {
+    if (!bytes || score < 0) return SALN_E_INVALID;
+    WfaAffParams prm{};
+    const int rc = make_params(pen, 0, &prm);
+    if (rc != SALN_OK) return rc;
+    *bytes = trace_layout(prm, len_q, len_db, score).bytes;
+    return SALN_OK;
+}
+
+int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                uint64_t n_pairs, const saln_wfa_penalties *pen,
+                                int32_t max_score, uint64_t trace_budget_bytes,
+                                saln_wfa_affine_aln **out) {
+    if (!ctx || !q_off || !db_off || !out) return SALN_E_INVALID;
+    auto aln = std::make_unique<saln_wfa_affine_aln>();
+    if (n_pairs == 0) {
+        aln->off.assign(1, 0);
+        *out = aln.release();
+        return SALN_OK;
+    }
+    // the score passes (saln_wfa_affine_batch's plan), sequences kept on the device
+    saln_wfa_affine_plan *plan = nullptr;
+    int rc = saln_wfa_affine_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs,
+                                         pen, max_score, &plan);
+    if (rc != SALN_OK) return rc;
+    aln->res.assign(n_pairs, saln_wfa_affine_result{});
+    aln->off.assign(n_pairs + 1, 0);
+    struct Guard {
+        saln_context *ctx;
+        saln_wfa_affine_plan *p;
+        std::vector<void *> bufs;
+        ~Guard() {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (void *b : bufs) dev_free(ctx, b);
+            saln_wfa_affine_plan_destroy(p);
+        }
+    } g{ctx, plan, {}};
+    auto alloc = [&](void **p, size_t n) {
+        const hipError_t e = dev_alloc(ctx, p, std::max<size_t>(n, 16));
+        if (e == hipSuccess) g.bufs.push_back(*p);
+        return e;
+    };
+    std::vector<WfaAffPair> hp;
+    {
+        bool wide = false;
+        uint64_t seq_need = 0, code_need = 0;
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &wide, &seq_need,
+                         &code_need);
+        if (rc != SALN_OK) return rc;
+    }
+    for (const WfaAffPair &p : hp)  // a CIGAR run holds 2^28-1 columns
+        if (p.lq > 0x0FFFFFFFu || p.ld > 0x0FFFFFFFu) return SALN_E_INVALID;
+    const uint64_t qb = q_off[n_q], db = db_off[n_db];
+    void *dq = nullptr, *dd = nullptr, *dsc = nullptr;
+    TRY(alloc(&dq, qb + 16));
+    TRY(alloc(&dd, db + 16));
+    TRY(alloc(&dsc, n_pairs * sizeof(int32_t)));
+    if (qb) TRY(hipMemcpy(dq, q_seq, qb, hipMemcpyHostToDevice));
+    if (db) TRY(hipMemcpy(dd, db_seq, db, hipMemcpyHostToDevice));
+    rc = saln_wfa_affine_execute(plan, (const uint8_t *)dq, (const uint8_t *)dd, (int32_t *)dsc,
+                                 nullptr);
+    if (rc != SALN_OK) return rc;
+    TRY(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> scores(n_pairs);
+    TRY(hipMemcpy(scores.data(), dsc, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+
+    // chunks: pairs in pair order, at most `budget` bytes of trace workspace each
+    const uint64_t budget = trace_budget_bytes ? trace_budget_bytes : (1ull << 30);
+    const WfaAffParams &prm = plan->prm;
+    struct Chunk {
+        std::vector<WfaAffTracePair> tp;  // p.out: the pair's index in the batch
+        uint64_t bytes = 0, words = 0;
+    };
+    std::vector<Chunk> chunks;
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        saln_wfa_affine_result &r = aln->res[k];
+        r.score = scores[k];
+        r.status = SALN_OK;
+        if (r.score < 0) continue;
+        const bool empty = hp[k].lq == 0 || hp[k].ld == 0;
+        const TraceLayout lay = trace_layout(prm, hp[k].lq, hp[k].ld, r.score);
+        if (lay.bytes > budget) {
+            r.status = SALN_TRACE_CAP;
+            continue;
+        }
+        if (chunks.empty() || chunks.back().bytes + lay.bytes > budget ||
+            chunks.back().tp.size() >= (1u << 30))
+            chunks.emplace_back();
+        Chunk &c = chunks.back();
+        WfaAffTracePair tp{};
+        tp.p = hp[k];
+        tp.p.reserved = empty ? 0u : (uint32_t)lay.T;
+        tp.code_off = c.bytes;
+        tp.cig_off = c.words;
+        tp.wt = (uint32_t)lay.wt;
+        tp.cig_cap = 2 * tp.p.reserved + 1;
+        c.bytes += lay.bytes;
+        c.words += tp.cig_cap;
+        c.tp.push_back(tp);
+    }
+    uint64_t max_bytes = 0, max_words = 0, max_n = 0;
+    for (const Chunk &c : chunks) {
+        max_bytes = std::max(max_bytes, c.bytes);
+        max_words = std::max(max_words, c.words);
+        max_n = std::max<uint64_t>(max_n, c.tp.size());
+    }
+    void *d_tp = nullptr, *d_codes = nullptr, *d_words = nullptr, *d_status = nullptr,
+         *d_len = nullptr, *d_next = nullptr;
+    if (!chunks.empty()) {
+        TRY(alloc(&d_tp, max_n * sizeof(WfaAffTracePair)));
+        TRY(alloc(&d_codes, max_bytes));
+        TRY(alloc(&d_words, max_words * sizeof(uint32_t)));
+        TRY(alloc(&d_status, max_n * sizeof(int32_t)));
+        TRY(alloc(&d_len, max_n * sizeof(uint32_t)));
+        TRY(alloc(&d_next, 2 * sizeof(uint32_t)));
+    }
+    // Per chunk: the fill with the first ring over every pair, the fill with
+    // the second ring over the pairs the first left (kTraceRerun in their
+    // status), the walk, then status / lengths / CIGAR areas back.  Chunks
+    // and their pairs are in pair order, so the handle's words are appended.
+    std::vector<uint64_t> ids;
+    std::vector<int32_t> h_status;
+    std::vector<uint32_t> h_len, h_words;
+    hipStream_t s = ctx->stream;
+    uint64_t next_pair = 0;  // pairs before it have their offset
+    for (Chunk &c : chunks) {
+        const uint32_t n = (uint32_t)c.tp.size();
+        ids.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            ids[i] = c.tp[i].p.out;
+            c.tp[i].p.out = i;
+        }
+        TRY(hipMemcpy(d_tp, c.tp.data(), n * sizeof(WfaAffTracePair), hipMemcpyHostToDevice));
+        TRY(hipMemsetAsync(d_next, 0, 2 * sizeof(uint32_t), s));
+        const auto *dp = (const WfaAffTracePair *)d_tp;
+        TRY(launch_wfa_affine_trace(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, plan->p1,
+                                    plan->wide, /*rerun=*/false,
+                                    grid_for(plan->p1, plan->wide, n, ctx->device),
+                                    (uint32_t *)d_next, (uint8_t *)d_codes, (int32_t *)d_status, s));
+        TRY(launch_wfa_affine_trace(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, plan->p2,
+                                    plan->wide, /*rerun=*/true,
+                                    grid_for(plan->p2, plan->wide, n, ctx->device),
+                                    (uint32_t *)d_next + 1, (uint8_t *)d_codes,
+                                    (int32_t *)d_status, s));
+        TRY(launch_wfa_affine_walk(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, prm,
+                                   (uint8_t *)d_codes, (int32_t *)d_status, (uint32_t *)d_words,
+                                   (uint32_t *)d_len, s));
+        TRY(hipStreamSynchronize(s));
+        h_status.resize(n);
+        h_len.resize(n);
+        h_words.resize(c.words);
+        TRY(hipMemcpy(h_status.data(), d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        TRY(hipMemcpy(h_len.data(), d_len, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        TRY(hipMemcpy(h_words.data(), d_words, c.words * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) {
+            saln_wfa_affine_result &r = aln->res[ids[i]];
+            r.status = h_status[i] == SALN_OK ? SALN_OK : SALN_INTERNAL;
+            r.cigar_len = r.status == SALN_OK ? std::min(h_len[i], c.tp[i].cig_cap) : 0;
+            for (; next_pair <= ids[i]; ++next_pair) aln->off[next_pair] = aln->words.size();
+            aln->words.insert(aln->words.end(), h_words.begin() + c.tp[i].cig_off,
+                              h_words.begin() + c.tp[i].cig_off + r.cigar_len);
+        }
+        std::vector<WfaAffTracePair>().swap(c.tp);
+    }
+    for (; next_pair <= n_pairs; ++next_pair) aln->off[next_pair] = aln->words.size();
+    *out = aln.release();
+    return SALN_OK;
+}
+
+uint64_t saln_wfa_affine_aln_count(const saln_wfa_affine_aln *a) { return a ? a->res.size() : 0; }
+
+int saln_wfa_affine_aln_get(const saln_wfa_affine_aln *a, uint64_t pair,
+                            saln_wfa_affine_result *res, const uint32_t **cigar) {
+    if (!a || pair >= a->res.size()) return SALN_E_INVALID;
+    if (res) *res = a->res[pair];
+    if (cigar) *cigar = a->words.data() + a->off[pair];
+    return SALN_OK;
+}
+
+void saln_wfa_affine_aln_free(saln_wfa_affine_aln *a) { delete a; }
 
 }  // extern "C"

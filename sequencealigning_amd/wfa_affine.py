@@ -9,6 +9,11 @@ x = 4 mismatch, o = 2 gap open, e = 6 gap extend; a gap of length L costs
 o + L*e): the minimum penalty of a global alignment, on the GPU
 (wfa_affine_kernels.hip).  The checker is the Gotoh DP in
 ``oracle/refaffine.c``.
+
+``wfa_affine_align_batch`` / ``wfa_affine_align`` also return one optimal
+alignment per pair as a CIGAR in the NW paths' format
+(wfa_affine_trace_kernels.hip): '=' / 'X' columns, 'I' a query base against
+'-', 'D' a '-' against a db base (the db is the reference sequence).
 """
 from __future__ import annotations
 
@@ -17,11 +22,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .nw import pack_csr
+from .nw import CigarBatch, _decode_cigar, pack_csr
 
 DEFAULT_PENALTIES = (4, 2, 6)
 OVER_MAX_SCORE = -1   # penalty above max_score
 OVER_WIDTH = -2       # wavefront wider than the widest ring (2,048 diagonals)
+TRACE_CAP = _lib.TRACE_CAP    # per-pair status: trace codes larger than the whole budget
+INTERNAL = _lib.INTERNAL      # per-pair status: trace / score passes disagree (never expected)
 
 
 def _pen(penalties):
@@ -60,6 +67,96 @@ def wfa_affine(seq1: bytes, seq2: bytes, *, penalties=None, max_score: int = 0,
     """Minimum gap-affine penalty of one pair (seq1 = query, seq2 = db)."""
     return int(wfa_affine_batch([seq1], [seq2], [(0, 0)], penalties=penalties,
                                 max_score=max_score, device=device)[0])
+
+
+def _pair_args(queries, dbs, pairs):
+    qs, qo = pack_csr(queries)
+    ds, do = pack_csr(dbs)
+    if pairs is None:
+        n = (len(qo) - 1) * (len(do) - 1)
+        pq = pd = None
+    else:
+        pairs = np.asarray(pairs, np.uint32).reshape(-1, 2)
+        n = len(pairs)
+        pq = np.ascontiguousarray(pairs[:, 0])
+        pd = np.ascontiguousarray(pairs[:, 1])
+    return qs, qo, ds, do, pq, pd, n
+
+
+def wfa_affine_align_batch(queries, dbs, pairs=None, *, penalties=None, max_score: int = 0,
+                           trace_budget: int = 0, device: int = 0):
+    """Minimum gap-affine penalty and one optimal alignment per pair.
+    Returns (results, cigars): results is a structured array (score, status,
+    cigar_len; score as wfa_affine_batch), cigars a CigarBatch (pair k's
+    [(length, op), ...], empty where the pair has no alignment: a negative
+    score, or status TRACE_CAP when its trace codes alone exceed
+    trace_budget bytes; 0 selects 1 GiB per chunk).  pairs as wfa_affine_batch."""
+    qs, qo, ds, do, pq, pd, n = _pair_args(queries, dbs, pairs)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    L = _lib.lib()
+    pen = _pen(penalties)
+    h = C.c_void_p()
+    _lib.check(L.saln_wfa_affine_align_batch(
+        _lib.context(device), vp(qs), vp(qo), len(qo) - 1, vp(ds), vp(do), len(do) - 1, vp(pq),
+        vp(pd), n, C.byref(pen), int(max_score), int(trace_budget), C.byref(h)),
+        "saln_wfa_affine_align_batch")
+    try:
+        res = np.zeros(n, dtype=_lib.WFA_AFFINE_RESULT_DTYPE)
+        r = _lib.WfaAffineResult()
+        for k in range(n):
+            _lib.check(L.saln_wfa_affine_aln_get(h, k, C.byref(r), None),
+                       "saln_wfa_affine_aln_get")
+            res[k] = (r.score, r.status, r.cigar_len, 0)
+        total = int(res["cigar_len"].sum(dtype=np.uint64))
+        words = np.zeros(total, np.uint32)
+        if total:  # the handle's words are contiguous in pair order
+            cp = C.POINTER(C.c_uint32)()
+            _lib.check(L.saln_wfa_affine_aln_get(h, 0, None, C.byref(cp)),
+                       "saln_wfa_affine_aln_get")
+            C.memmove(words.ctypes.data, cp, 4 * total)
+    finally:
+        L.saln_wfa_affine_aln_free(h)
+    lens = res["cigar_len"].astype(np.uint64)
+    offs = np.zeros(n, np.uint64)
+    if n:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return res, CigarBatch(words, offs, lens)
+
+
+def wfa_affine_align(seq1: bytes, seq2: bytes, *, penalties=None, max_score: int = 0,
+                     trace_budget: int = 0, device: int = 0):
+    """(score, cigar) of one pair (seq1 = query, seq2 = db): cigar is the NW
+    path's [(n, op)] list (nw.alignment_rows prints it), empty without an
+    alignment (negative score, or a trace larger than trace_budget)."""
+    res, cig = wfa_affine_align_batch([seq1], [seq2], [(0, 0)], penalties=penalties,
+                                      max_score=max_score, trace_budget=trace_budget,
+                                      device=device)
+    return int(res["score"][0]), cig[0]
+
+
+def cigar_penalty(cigar, penalties=None) -> int:
+    """Gap-affine penalty of a CIGAR ([(n, op)]): x per 'X' column and
+    o + e * len per gap run ('I' or 'D'; an I run next to a D run is two gaps)."""
+    x, o, e = penalties if penalties is not None else DEFAULT_PENALTIES
+    total, prev = 0, None
+    for n, op in cigar:
+        if op == "X":
+            total += x * n
+        elif op in "ID":
+            total += e * n + (o if op != prev else 0)
+        prev = op
+    return total
+
+
+def trace_bytes(len_q: int, len_db: int, score: int, penalties=None) -> int:
+    """saln_wfa_affine_trace_bytes: bytes of trace workspace of one pair with
+    this penalty (host only; the layout is in DESIGN.md)."""
+    pen = _pen(penalties)
+    out = C.c_uint64()
+    _lib.check(_lib.lib().saln_wfa_affine_trace_bytes(C.byref(pen), int(len_q), int(len_db),
+                                                      int(score), C.byref(out)),
+               "saln_wfa_affine_trace_bytes")
+    return out.value
 
 
 class WfaAffinePlan:
