@@ -127,7 +127,9 @@ int saln_abi_version(void);
  * defaults.  No reference counterpart: the reference has no tuning (its
  * constants are compile-time, needleman_wunsch_affine.rs:15-20).  The engine
  * reads nothing from the process environment; these calls are the only way
- * to change what it runs.  Every option gives the same results.  Names:
+ * to change what it runs.  Every option gives the same results (but one: a
+ * narrower second ring of the corrected WFA returns -2 for pairs that a wider
+ * one scores).  Names:
  * "nw.wide_min_pairs", "nw.rows_k", "nw.stripe_pk", "nw.spec",
  * "nw.spec_passes", "nw.spec_strict", "nw.avsa_narrow", "nw.rows_lone",
  * "nw.rows_xcd", "nw.avsa_profile", "nw.pk_tab", "nw.walk_waves",
@@ -138,7 +140,9 @@ int saln_abi_version(void);
  *    choices; another context is not affected).
  * A plan, all-vs-all handle, span or host-buffer call takes its context's
  * effective values when it is created (or called); a later change does not
- * reach it.  SALN_E_INVALID for an unknown name or a value out of range. */
+ * reach it.  SALN_E_INVALID for an unknown name or a value out of range.
+ * The two ring-width options of the corrected WFA are stored within 0..4096,
+ * but that engine runs only 0, 512, 1024 and 2048 (see saln_wfa_affine_batch). */
 int saln_option_set(const char *name, int64_t value);
 int saln_option_get(const char *name, int64_t *value, int64_t *default_value);
 /* Name of option `index` (0, 1, ...; SALN_E_INVALID past the last). */
@@ -560,8 +564,22 @@ int saln_wfa_plan_destroy(saln_wfa_plan *plan);
  * gaps, with the reference's penalties (wfa.rs:14-21) by default.  The
  * checker is the Gotoh DP (oracle/refaffine.c).
  * scores[p] >= 0: the penalty; -1: above max_score (max_score <= 0: no cap);
- * -2: the wavefront grew past 2,048 diagonals (i16 offsets; 1,024 for a
- * sequence longer than 32,000 bases). */
+ * -2: the wavefront grew past the second pass's ring: 2,048 diagonals with
+ * the default penalties (i16 offsets; 1,024 when a sequence of the batch is
+ * longer than 32,000 bases, which selects i32 offsets), fewer where the
+ * penalties need more ring slots (saln_wfa_affine_plan_geometry reports the
+ * widths).
+ * Ring widths and LDS: a pass's rings take 768 + (RM + 2 RI) * W * (2 | 4)
+ * bytes of LDS for W diagonals, RM = max(x, o+e) / g + 1 and RI = e / g + 1
+ * slots (g = gcd(x, o+e, e); at most 16 each, else SALN_E_INVALID) and i16 |
+ * i32 offsets.  No pass asks for more than the 65,536 bytes of a workgroup:
+ * a pass whose rings do not fit at its width ("wfa2.w1" / "wfa2.w2", or the
+ * default) runs the widest of 2,048, 1,024 and 512 diagonals that fits, and
+ * penalties whose rings do not fit at 512 are refused (SALN_E_INVALID with a
+ * message naming them).  The kernels run rings of 512, 1,024 and 2,048
+ * diagonals only: with "wfa2.w1" or "wfa2.w2" at any other value but 0
+ * (the default width) every plan, batch and geometry call returns
+ * SALN_E_INVALID. */
 typedef struct {
     int32_t mismatch;   /* x = 4 */
     int32_t gap_open;   /* o = 2 */
@@ -634,6 +652,29 @@ void saln_wfa_affine_aln_free(saln_wfa_affine_aln *a);
  * penalties. */
 int saln_wfa_affine_trace_bytes(const saln_wfa_penalties *pen, uint64_t len_q, uint64_t len_db,
                                 int32_t score, uint64_t *bytes);
+/* Host only (no device needed): the launch geometry a plan over pairs of
+ * these lengths (len_q[k] x len_db[k]) takes with these penalties and the
+ * process registry's options - the decision saln_wfa_affine_plan_create
+ * makes (with its context's options).  out[0] is the first pass, out[1] the
+ * second (the pairs whose wavefront outgrew the first ring).  seqcap: the
+ * LDS bytes for a pair's staged sequences; a pair stages 2-bit codes when
+ * 4 * ((a_q + len_q + 15) / 16 + (a_d + len_db + 15) / 16 + 4) <= seqcap
+ * (a_*: the sequence's address & 15) and all its bytes are A, C, G, T; else
+ * bytes when ((len_q + 47) & ~15) + len_db + 48 <= seqcap; else it reads
+ * the sequences where they are.  SALN_E_INVALID as the plan: bad penalties,
+ * a refused ring-width option, rings that do not fit LDS. */
+typedef struct {
+    int32_t ring_width;   /* diagonals per wavefront slot: 512, 1024 or 2048 */
+    int32_t seqcap;       /* LDS bytes for staged sequences (0: none staged) */
+    uint32_t lds_bytes;   /* dynamic LDS of a workgroup: rings + seqcap, <= 65,536 */
+    int32_t i32_offsets;  /* 1: i32 wavefront offsets (a sequence above 32,000 bases) */
+    uint32_t workgroups_per_cu; /* a launch of n pairs (a score pass, or a trace fill of one
+                                 * chunk) runs min(n, workgroups_per_cu * CUs) one-wave
+                                 * workgroups, which take the pairs from a counter */
+} saln_wfa_affine_pass_geometry;   /* 20 bytes */
+int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t *len_q,
+                                  const uint64_t *len_db, uint64_t n_pairs,
+                                  saln_wfa_affine_pass_geometry out[2]);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

@@ -95,6 +95,12 @@ class WfaAffineResult(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class WfaAffinePassGeometry(C.Structure):
+    """saln_wfa_affine_pass_geometry: one pass of saln_wfa_affine_plan_geometry."""
+    _fields_ = [("ring_width", C.c_int32), ("seqcap", C.c_int32), ("lds_bytes", C.c_uint32),
+                ("i32_offsets", C.c_int32), ("workgroups_per_cu", C.c_uint32)]
+
+
 WFA_AFFINE_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("cigar_len", "<u4"),
                            ("reserved", "<u4")]
 
@@ -121,7 +127,7 @@ EXPORTS = [
     "saln_wfa_affine_batch", "saln_wfa_affine_plan_create", "saln_wfa_affine_execute",
     "saln_wfa_affine_plan_destroy",
     "saln_wfa_affine_align_batch", "saln_wfa_affine_aln_count", "saln_wfa_affine_aln_get",
-    "saln_wfa_affine_aln_free", "saln_wfa_affine_trace_bytes",
+    "saln_wfa_affine_aln_free", "saln_wfa_affine_trace_bytes", "saln_wfa_affine_plan_geometry",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -264,6 +270,8 @@ def lib() -> C.CDLL:
         L.saln_wfa_affine_aln_free.restype = None
         L.saln_wfa_affine_trace_bytes.argtypes = [C.POINTER(WfaPenalties), C.c_uint64,
                                                   C.c_uint64, C.c_int32, u64p]
+        L.saln_wfa_affine_plan_geometry.argtypes = [C.POINTER(WfaPenalties), vp, vp, C.c_uint64,
+                                                    C.POINTER(WfaAffinePassGeometry)]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

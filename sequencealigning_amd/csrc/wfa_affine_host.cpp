@@ -7,7 +7,9 @@
 //
 // Two passes: every pair first runs with a W-diagonal wavefront ring; pairs
 // whose wavefront outgrows it (score -2) are compacted on the device and run
-// again with a 2x wider ring.  Score -1: the penalty exceeds max_score.
+// again with the second pass's ring (2x wider by default; plan_passes decides
+// both widths and keeps each pass within the 64 KB of LDS of a workgroup).
+// Score -1: the penalty exceeds max_score.
 //
 // Alignment mode (saln_wfa_affine_align_batch): the score passes, the scores
 // read back, then per chunk of at most trace_budget_bytes of trace workspace
@@ -42,10 +44,14 @@ struct saln_wfa_affine_plan {
 
 namespace {
 
-// ring widths (diagonals) of the two passes, i16 / i32 offsets: the second
-// pass's ring is the 64 KB LDS limit of a workgroup; a wavefront wider than it
-// (|k| > W/2 diagonals: penalties above ~e * W / 2) leaves score -2
+// ring widths (diagonals) of the two passes, i16 / i32 offsets: with the
+// default penalties the second pass's ring is the 64 KB LDS limit of a
+// workgroup; a wavefront wider than it leaves score -2.  plan_passes narrows
+// a pass whose penalties need more ring slots than fit at these widths.
 constexpr int32_t kW1 = 1024, kW2 = 2048, kW1Wide = 512, kW2Wide = 1024;
+constexpr uint64_t kLdsLimit = 64u << 10;  // dynamic LDS of one workgroup
+constexpr uint64_t kI16MaxLen = 32000;     // longest sequence of a plan with i16 offsets
+constexpr uint64_t kMaxLen = 0x3FFFFFFFull;  // longest sequence the engine takes
 
 #define TRY(expr)                                                                          \
     do {                                                                                   \
@@ -74,21 +80,89 @@ int make_params(const saln_wfa_penalties *pen, int32_t max_score, WfaAffParams *
     return SALN_OK;
 }
 
+// Workgroups (waves) of a persistent launch per CU: as many as 160 KB of LDS
+// hold, at most 16.  grid_for and the geometry query both use it.
+uint32_t workgroups_per_cu(const WfaAffParams &prm, bool wide) {
+    const size_t lds = wfa_affine_lds_bytes(prm, wide);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (160u << 10) / lds));
+}
+
 uint32_t grid_for(const WfaAffParams &prm, bool wide, uint64_t n, int device) {
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const size_t lds = wfa_affine_lds_bytes(prm, wide);
-    const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(16, (160u << 10) / lds));
-    (void)wide;
+    const uint64_t per_cu = workgroups_per_cu(prm, wide);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, per_cu * (uint64_t)cus));
+}
+
+// What a plan's passes depend on besides the penalties, folded over the
+// batch's pairs (build_pairs and saln_wfa_affine_plan_geometry): the longest
+// sequence (i32 offsets above kI16MaxLen bases) and the worst-case staging needs.
+struct BatchShape {
+    uint64_t maxlen = 0, seq_need = 0, code_need = 0;
+    bool wide() const { return maxlen > kI16MaxLen; }
+    // false: a sequence longer than the engine takes
+    bool add(uint64_t lq, uint64_t ld) {
+        if (lq > kMaxLen || ld > kMaxLen) return false;
+        maxlen = std::max({maxlen, lq, ld});
+        // LDS bytes to stage both sequences (wfa_affine_kernel's layout)
+        seq_need = std::max<uint64_t>(seq_need, ((lq + 47) & ~15ull) + ld + 48);
+        // ... or as 2-bit codes (16 per word, the 16-byte-aligned base's
+        // words plus two pad words per sequence)
+        // (at any alignment of the caller's buffers)
+        code_need = std::max<uint64_t>(code_need, 4 * ((15 + lq + 15) / 16 + 2 + (15 + ld + 15) / 16 + 2));
+        return true;
+    }
+};
+
+// The two passes of a plan (ring width, LDS sequence staging): pure host
+// logic, shared by saln_wfa_affine_plan_create and
+// saln_wfa_affine_plan_geometry.  Each pass stages the pair's sequences in
+// LDS when they fit next to its rings within wfa2.seq_lds / the 64 KB
+// workgroup limit (else reads HBM).  The kernels index a ring with
+// k & (W - 1) and run 512, 1024 or 2048 diagonals, so any other requested
+// width is refused; a pass whose rings do not fit the workgroup limit at the
+// requested width takes the widest of those that does.
+int plan_passes(const WfaAffParams &prm, bool wide, uint64_t seq_need, uint64_t code_need,
+                const Options &opts, WfaAffParams *p1, WfaAffParams *p2) {
+    // tuning options (saln_option_set): staged-sequence LDS, ring widths (0 auto)
+    const uint64_t seq_lds = (uint64_t)opts[Opt::Wfa2SeqLds];
+    const int64_t w[2] = {opts[Opt::Wfa2W1], opts[Opt::Wfa2W2]};
+    WfaAffParams *out[2] = {p1, p2};
+    for (int i = 0; i < 2; ++i) {
+        if (w[i] != 0 && w[i] != 512 && w[i] != 1024 && w[i] != 2048) {
+            set_error(std::string("wfa_affine: option wfa2.w") + (i ? "2" : "1") + " = " +
+                      std::to_string(w[i]) + " is not a ring width the kernels run (0, 512, 1024, 2048)");
+            return SALN_E_INVALID;
+        }
+        WfaAffParams q = prm;
+        q.seqcap = 0;
+        q.W = w[i] ? (int32_t)w[i] : wide ? (i ? kW2Wide : kW1Wide) : (i ? kW2 : kW1);
+        while (q.W > 512 && wfa_affine_lds_bytes(q, wide) > kLdsLimit) q.W >>= 1;
+        const uint64_t rings = wfa_affine_lds_bytes(q, wide);
+        if (rings > kLdsLimit) {
+            set_error("wfa_affine: the wavefront rings of penalties (" + std::to_string(prm.x) + ", " +
+                      std::to_string(prm.o) + ", " + std::to_string(prm.e) + ") with " +
+                      (wide ? "i32" : "i16") + " offsets need " + std::to_string(rings) +
+                      " bytes of LDS at 512 diagonals, above the 65,536 of a workgroup");
+            return SALN_E_INVALID;
+        }
+        const uint64_t cap = std::min<uint64_t>(seq_lds, kLdsLimit - rings);
+        // 2-bit codes when they fit (a pair holding other bytes then reads
+        // HBM), bytes too when they take little more: the kernel tries codes
+        // first, then bytes, within seqcap
+        uint64_t want = code_need <= cap ? code_need : 0;
+        if (seq_need <= cap && seq_need <= std::max<uint64_t>(want, 8u << 10)) want = std::max(want, seq_need);
+        // (rings is a multiple of 16, so the rounding stays within the limit)
+        q.seqcap = (int32_t)std::min<uint64_t>((want + 15) & ~15ull, kLdsLimit - rings);
+        *out[i] = q;
+    }
+    return SALN_OK;
 }
 
 int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
                 const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
-                std::vector<WfaAffPair> *out, bool *wide, uint64_t *seq_need,
-                uint64_t *code_need) {
+                std::vector<WfaAffPair> *out, BatchShape *shape) {
     out->resize(n_pairs);
-    uint64_t maxlen = 0;
     for (uint64_t k = 0; k < n_pairs; ++k) {
         const uint64_t qi = pair_q ? pair_q[k] : k % n_q, di = pair_db ? pair_db[k] : k / n_q;
         if (qi >= n_q || di >= n_db) return SALN_E_INVALID;
@@ -96,20 +170,12 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
         p.q_off = q_off[qi];
         p.d_off = db_off[di];
         const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        if (lq > 0x3FFFFFFFull || ld > 0x3FFFFFFFull) return SALN_E_INVALID;
+        if (!shape->add(lq, ld)) return SALN_E_INVALID;
         p.lq = (uint32_t)lq;
         p.ld = (uint32_t)ld;
         p.out = (uint32_t)k;
-        maxlen = std::max({maxlen, lq, ld});
-        // LDS bytes to stage both sequences (wfa_affine_kernel's layout)
-        *seq_need = std::max<uint64_t>(*seq_need, ((lq + 47) & ~15ull) + ld + 48);
-        // ... or as 2-bit codes (16 per word, the 16-byte-aligned base's
-        // words plus two pad words per sequence)
-        // (at any alignment of the caller's buffers)
-        *code_need = std::max<uint64_t>(*code_need, 4 * ((15 + lq + 15) / 16 + 2 + (15 + ld + 15) / 16 + 2));
         (*out)[k] = p;
     }
-    *wide = maxlen > 32000;
     return SALN_OK;
 }
 
@@ -157,10 +223,14 @@ int saln_wfa_affine_plan_create(saln_context *ctx, const uint64_t *q_off, uint64
     p->ctx = ctx;
     int rc = make_params(pen, max_score, &p->prm);
     std::vector<WfaAffPair> hp;
-    uint64_t seq_need = 0, code_need = 0;
+    BatchShape shape;
+    if (rc == SALN_OK) rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &shape);
+    p->wide = shape.wide();
+    // the passes before anything touches the device: a refused ring width or
+    // penalty set never reaches an allocation or a launch
     if (rc == SALN_OK)
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &p->wide,
-                         &seq_need, &code_need);
+        rc = plan_passes(p->prm, p->wide, shape.seq_need, shape.code_need,
+                         ctx->opts.effective(), &p->p1, &p->p2);
     if (rc != SALN_OK) {
         delete p;
         return rc;
@@ -181,29 +251,6 @@ int saln_wfa_affine_plan_create(saln_context *ctx, const uint64_t *q_off, uint64
                            hipMemcpyHostToDevice)) != hipSuccess)
             return fail(e);
     }
-    // Each pass stages the pair's sequences in LDS when they fit next to its
-    // rings within kSeqLds / the 64 KB workgroup limit (else reads HBM).
-    // tuning options (saln_option_set): staged-sequence LDS, ring widths (0 auto)
-    const Options opts = ctx->opts.effective();
-    const uint64_t seq_lds = (uint64_t)opts[Opt::Wfa2SeqLds];
-    const int32_t w1 = (int32_t)opts[Opt::Wfa2W1];
-    const int32_t w2 = (int32_t)opts[Opt::Wfa2W2];
-    auto pass = [&](int32_t W) {
-        WfaAffParams q = p->prm;
-        q.W = W;
-        q.seqcap = 0;
-        const size_t rings = wfa_affine_lds_bytes(q, p->wide);
-        const uint64_t cap = std::min<uint64_t>(seq_lds, (64u << 10) - rings);
-        // 2-bit codes when they fit (a pair holding other bytes then reads
-        // HBM), bytes too when they take little more: the kernel tries codes
-        // first, then bytes, within seqcap
-        uint64_t want = code_need <= cap ? code_need : 0;
-        if (seq_need <= cap && seq_need <= std::max<uint64_t>(want, 8u << 10)) want = std::max(want, seq_need);
-        q.seqcap = (int32_t)((want + 15) & ~15ull);
-        return q;
-    };
-    p->p1 = pass(w1 ? w1 : p->wide ? kW1Wide : kW1);
-    p->p2 = pass(w2 ? w2 : p->wide ? kW2Wide : kW2);
     p->grid1 = grid_for(p->p1, p->wide, n_pairs, ctx->device);
     p->grid2 = grid_for(p->p2, p->wide, n_pairs, ctx->device);
     *out = p;
@@ -282,6 +329,29 @@ int saln_wfa_affine_trace_bytes(const saln_wfa_penalties *pen, uint64_t len_q, u
     return SALN_OK;
 }
 
+int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t *len_q,
+                                  const uint64_t *len_db, uint64_t n_pairs,
+                                  saln_wfa_affine_pass_geometry *out) {
+    if (!out || (n_pairs && (!len_q || !len_db))) return SALN_E_INVALID;
+    WfaAffParams prm{}, pass[2];
+    int rc = make_params(pen, 0, &prm);
+    if (rc != SALN_OK) return rc;
+    BatchShape shape;
+    for (uint64_t k = 0; k < n_pairs; ++k)
+        if (!shape.add(len_q[k], len_db[k])) return SALN_E_INVALID;
+    const bool wide = shape.wide();
+    rc = plan_passes(prm, wide, shape.seq_need, shape.code_need, opt_registry(), &pass[0], &pass[1]);
+    if (rc != SALN_OK) return rc;
+    for (int i = 0; i < 2; ++i) {
+        out[i].ring_width = pass[i].W;
+        out[i].seqcap = pass[i].seqcap;
+        out[i].lds_bytes = (uint32_t)wfa_affine_lds_bytes(pass[i], wide);
+        out[i].i32_offsets = wide ? 1 : 0;
+        out[i].workgroups_per_cu = workgroups_per_cu(pass[i], wide);
+    }
+    return SALN_OK;
+}
+
 int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
                                 uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
                                 uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
@@ -319,10 +389,8 @@ int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const u
     };
     std::vector<WfaAffPair> hp;
     {
-        bool wide = false;
-        uint64_t seq_need = 0, code_need = 0;
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &wide, &seq_need,
-                         &code_need);
+        BatchShape shape;
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &shape);
         if (rc != SALN_OK) return rc;
     }
     for (const WfaAffPair &p : hp)  // a CIGAR run holds 2^28-1 columns

@@ -26,7 +26,9 @@ from .nw import CigarBatch, _decode_cigar, pack_csr
 
 DEFAULT_PENALTIES = (4, 2, 6)
 OVER_MAX_SCORE = -1   # penalty above max_score
-OVER_WIDTH = -2       # wavefront wider than the widest ring (2,048 diagonals)
+OVER_WIDTH = -2       # wavefront wider than the second pass's ring: 2,048 diagonals with
+#                       the default penalties, fewer where the penalties need more ring
+#                       slots or a sequence is above 32,000 bases (plan_geometry reports it)
 TRACE_CAP = _lib.TRACE_CAP    # per-pair status: trace codes larger than the whole budget
 INTERNAL = _lib.INTERNAL      # per-pair status: trace / score passes disagree (never expected)
 
@@ -157,6 +159,25 @@ def trace_bytes(len_q: int, len_db: int, score: int, penalties=None) -> int:
                                                       int(score), C.byref(out)),
                "saln_wfa_affine_trace_bytes")
     return out.value
+
+
+def plan_geometry(lengths, penalties=None):
+    """saln_wfa_affine_plan_geometry (host only): the two passes a plan over
+    pairs of these (len_q, len_db) takes with the process's options, as a
+    list of two dicts (ring_width, seqcap, lds_bytes, i32_offsets,
+    workgroups_per_cu).  Raises
+    SalnError (E_INVALID) where the plan would be refused."""
+    lens = np.asarray(list(lengths), np.uint64).reshape(-1, 2)
+    lq = np.ascontiguousarray(lens[:, 0])
+    ld = np.ascontiguousarray(lens[:, 1])
+    pen = _pen(penalties)
+    out = (_lib.WfaAffinePassGeometry * 2)()
+    _lib.check(_lib.lib().saln_wfa_affine_plan_geometry(
+        C.byref(pen), lq.ctypes.data_as(C.c_void_p), ld.ctypes.data_as(C.c_void_p), len(lens),
+        out), "saln_wfa_affine_plan_geometry")
+    return [dict(ring_width=g.ring_width, seqcap=g.seqcap, lds_bytes=g.lds_bytes,
+                 i32_offsets=bool(g.i32_offsets), workgroups_per_cu=g.workgroups_per_cu)
+            for g in out]
 
 
 class WfaAffinePlan:

@@ -4,8 +4,9 @@ CIGAR goes through one checker: run-length maximal, consumes both sequences
 exactly, '=' columns equal and 'X' columns different, and its gap-affine
 penalty equals both the returned score and the Gotoh DP's minimum
 (oracle/refaffine.c)."""
-import numpy as np
 import pytest
+
+from wfa_affine_model import check_cigar, mixed_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -13,59 +14,8 @@ PENS = [(4, 2, 6), (1, 3, 1), (5, 0, 2), (3, 5, 1)]
 
 
 def _pairs(seed):
-    """The recipe of test_wfa_affine_gpu.py::_pairs."""
-    from sequencealigning_amd import synth
-    rng = np.random.default_rng(seed)
-    qs, ds = [], []
-    for k in range(96):
-        kind = k % 6
-        lq = int(rng.integers(1, 400))
-        if kind == 0:   # i.i.d.
-            q = synth.random_bases(seed * 1000 + k, lq).tobytes()
-            d = synth.random_bases(seed * 1000 + k + 500, int(rng.integers(1, 400))).tobytes()
-        elif kind == 1:  # mutated 5 %
-            q = synth.random_bases(seed * 1000 + k, lq).tobytes()
-            d = synth.mutate(q, 0.05, seed=k)
-        elif kind == 2:  # mutated 20 %
-            q = synth.random_bases(seed * 1000 + k, lq).tobytes()
-            d = synth.mutate(q, 0.2, seed=k)
-        elif kind == 3:  # repetitive, 2 letters
-            q = bytes(rng.choice([65, 67], lq).astype(np.uint8))
-            d = bytes(rng.choice([65, 67], int(rng.integers(1, 400))).astype(np.uint8))
-        elif kind == 4:  # identical / prefix
-            q = synth.random_bases(seed * 1000 + k, lq).tobytes()
-            d = q[: int(rng.integers(0, lq + 1))]
-        else:           # lopsided, with N
-            q = bytes(rng.choice(list(b"ACGTN"), int(rng.integers(1, 30))).astype(np.uint8))
-            d = bytes(rng.choice(list(b"ACGTN"), int(rng.integers(100, 500))).astype(np.uint8))
-        qs.append(q)
-        ds.append(d)
-    qs += [b"", b"A", b"", b"ACGT"]
-    ds += [b"", b"", b"ACG", b"ACGT"]
-    return qs, ds
-
-
-def check_cigar(saln, q, d, cigar, score, pen, want=None):
-    """The shared checker; want: the DP's penalty (None: not compared)."""
-    for (n, op), nxt in zip(cigar, cigar[1:] + [(1, None)]):
-        assert n > 0 and op in "=XID" and op != nxt[1], cigar
-    i = j = 0  # db, query
-    for n, op in cigar:
-        if op in "=X":
-            a = np.frombuffer(q, np.uint8, n, j)
-            b = np.frombuffer(d, np.uint8, n, i)
-            assert ((a == b) if op == "=" else (a != b)).all(), (op, i, j)
-            i += n
-            j += n
-        elif op == "I":
-            j += n
-        else:
-            i += n
-        assert j <= len(q) and i <= len(d)
-    assert (j, i) == (len(q), len(d))
-    assert saln.wfa_affine.cigar_penalty(cigar, pen) == score
-    if want is not None:
-        assert score == want
+    """96 mixed pairs of up to 400 (db: 500) bases and four fixed ones."""
+    return mixed_pairs(seed)
 
 
 @pytest.fixture(scope="module")
