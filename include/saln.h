@@ -133,7 +133,8 @@ int saln_abi_version(void);
  * "nw.wide_min_pairs", "nw.rows_k", "nw.stripe_pk", "nw.spec",
  * "nw.spec_passes", "nw.spec_strict", "nw.avsa_narrow", "nw.rows_lone",
  * "nw.rows_xcd", "nw.avsa_profile", "nw.pk_tab", "nw.walk_waves",
- * "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "host.timing", "host.prefault_mb".
+ * "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb", "host.timing",
+ * "host.prefault_mb".
  * Two levels, no other shared state:
  *  - saln_option_*: the process registry, the default of every context;
  *  - saln_context_option_*: overrides of one context (its own thread's
@@ -142,7 +143,15 @@ int saln_abi_version(void);
  * effective values when it is created (or called); a later change does not
  * reach it.  SALN_E_INVALID for an unknown name or a value out of range.
  * The two ring-width options of the corrected WFA are stored within 0..4096,
- * but that engine runs only 0, 512, 1024 and 2048 (see saln_wfa_affine_batch). */
+ * but that engine runs only 0, 512, 1024 and 2048 (see saln_wfa_affine_batch).
+ * The arena option (MB, default 32768, minimum 1) bounds the tensor history
+ * that one launch of the reference-semantics WFA (saln_wfa_*) keeps.  A lane
+ * (one pair) of a pass with step cap s and width W holds S = s / 2 + 1 tensor
+ * slots, S * 48 + S * 3 * W * 8 + S bytes.  A launch takes budget / that many
+ * lanes, where the budget is the option's value or half of the free device
+ * memory if that is less, but never fewer than 256 lanes (or the whole batch
+ * if it is smaller); a batch with more pairs runs in several launches.  The
+ * results do not depend on it. */
 int saln_option_set(const char *name, int64_t value);
 int saln_option_get(const char *name, int64_t *value, int64_t *default_value);
 /* Name of option `index` (0, 1, ...; SALN_E_INVALID past the last). */
@@ -490,7 +499,21 @@ int saln_device_cu_probe(saln_context *ctx, void *stream, uint32_t n_blocks, uin
  * (status SALN_NONCONVERGED), and max_width bounds a wavefront's width
  * (also SALN_NONCONVERGED).  Rust panics are statuses:
  * SALN_REF_PANIC_TRIM (rotate_left / expect / unwrap in trim),
- * SALN_REF_PANIC_SLICE (slice indexing in rec_tr). */
+ * SALN_REF_PANIC_SLICE (slice indexing in rec_tr).
+ *
+ * The two caps.  Results equal the reference's until one of them binds:
+ *  - step cap: the pair has made max_steps expand calls without converging.
+ *    status SALN_NONCONVERGED, steps == max_steps, score == steps + 1 (every
+ *    expand call pushed its tensor, and score is wfs.len()).
+ *  - width cap: an expand call would build a tensor of more than max_width
+ *    diagonals (hi - lo + 1 of the `lo/hi` line it prints; the line is still
+ *    printed by saln_wfa_render).  status SALN_NONCONVERGED, steps counts
+ *    the refused call, score == steps (its tensor was not pushed).
+ * steps < max_steps tells the width cap from the step cap.  The tensor of
+ * the k-th expand call is at most 2 * (k / 4) + 1 diagonals wide (integer
+ * division: its sources lie 4, 6 and 8 calls back and each side grows by
+ * one), so max_width >= 2 * (max_steps / 4) + 1 never binds; the default
+ * width of 64 cannot bind for max_steps <= 127. */
 typedef struct {
     int32_t score;        /* printed score: wfs.len() at convergence (:33-38) */
     int32_t status;       /* SALN_OK | SALN_NOT_IMPLEMENTED | SALN_REF_PANIC_* | SALN_NONCONVERGED */
@@ -544,8 +567,9 @@ void saln_wfa_text_free(saln_wfa_text *t);
 /* Device-resident WFA batch (configs[2] / C3 measurement): plan once from host
  * offsets and a pair list (NULL = all-vs-all, reference order), then execute
  * on device sequences (same CSR layout) into device results[n_pairs].  No
- * alignment rows.  Pairs that reach a 64-step first pass are re-run with
- * max_steps; the results equal a single pass at max_steps. */
+ * alignment rows.  With max_steps above 32, pairs that reach a 32-step first
+ * pass are re-run with max_steps (saln_wfa_align_batch does the same); the
+ * results equal a single pass at max_steps. */
 typedef struct saln_wfa_plan saln_wfa_plan;
 int saln_wfa_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
                          const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,

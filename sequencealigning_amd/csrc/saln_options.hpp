@@ -33,6 +33,7 @@ enum class Opt : int {
     Wfa2SeqLds,         // "wfa2.seq_lds": LDS bytes for staged sequences (corrected WFA)
     Wfa2W1,             // "wfa2.w1": first-pass ring width (0 auto)
     Wfa2W2,             // "wfa2.w2": second-pass ring width (0 auto)
+    WfaArenaMb,         // "wfa.arena_mb": MB of tensor history per launch (reference-semantics WFA)
     HostTiming,         // "host.timing": stage times of the host paths on stderr
     HostPrefaultMb,     // "host.prefault_mb": host buffer a new context faults in while HIP starts
     Count

@@ -41,9 +41,11 @@ struct DevBuf {
 };
 
 constexpr uint32_t kDefaultSteps = 64, kDefaultWidth = 64;
-// bytes of tensor history per launch: sized for 288 GB of HBM, capped by the
-// free memory at plan time (WfaScratch::arena)
-constexpr uint64_t kArenaBudget = 32ull << 30;
+// Tensor history per launch: "wfa.arena_mb" (default 32 GB, sized for 288 GB of
+// HBM), capped by the free memory at plan time (WfaScratch::arena).
+uint64_t arena_budget(const saln_context *ctx) {
+    return (uint64_t)ctx->opts.effective()[Opt::WfaArenaMb] << 20;
+}
 // Batch runs start every pair with this step cap (a small arena, many lanes
 // per launch); the pairs that reach it are re-run with the caller's cap.
 // Essentially every realistic pair ends far earlier (REF_PANIC_TRIM at s = 20,
@@ -64,12 +66,14 @@ struct WfaScratch {
     uint64_t S = 0, W = 0, nl = 0;
     DevBuf rerun, cnt;
     uint64_t rerun_n = 0;
+    uint64_t budget_bytes = 0;  // arena_budget() of the owner's context
 
+    // Lanes per launch: budget / per_lane, at least 256, at most n_pairs.
     hipError_t arena(uint64_t S_, uint64_t W_, uint64_t n_pairs, WfaArena *out) {
         const uint64_t per_lane = S_ * 3 * 4 * 4 + S_ * 3 * W_ * 8 + S_;
-        // at most kArenaBudget, and at most half of the device memory free
-        // now (the arena held so far counts as free: it is replaced)
-        uint64_t budget = kArenaBudget;
+        // at most the option's budget, and at most half of the device memory
+        // free now (the arena held so far counts as free: it is replaced)
+        uint64_t budget = budget_bytes;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
             const uint64_t held = S * 3 * 4 * 4 * nl + S * 3 * W * 8 * nl + S * nl;
@@ -219,6 +223,7 @@ int run_wfa(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint
         TRY_HIP(de.alloc(n_pairs * (uint64_t)ev_cap));
     }
     WfaScratch ws;
+    ws.budget_bytes = arena_budget(ctx);
     rc = wfa_device(ws, (const WfaPairDesc *)dp.p, (uint32_t)n_pairs, (const uint8_t *)dq.p,
                     (const uint8_t *)dd.p, max_steps, max_width, (saln_wfa_result *)dr.p,
                     (uint8_t *)da.p, (int32_t *)dl.p, (uint8_t *)de.p, ev_cap, ctx->stream);
@@ -498,6 +503,7 @@ int saln_wfa_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     p->n_pairs = (uint32_t)n_pairs;
     p->max_steps = max_steps ? max_steps : kDefaultSteps;
     p->max_width = max_width ? max_width : kDefaultWidth;
+    p->ws.budget_bytes = arena_budget(ctx);
     std::vector<WfaPairDesc> descs;
     uint64_t ab = 0;
     int rc = build_descs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, mode, nullptr, 0,

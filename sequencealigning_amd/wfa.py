@@ -50,10 +50,12 @@ def render(seq1, seq2, mode: Mode = Mode.Global, *, max_steps: int = 64, max_wid
 
 
 def render_batch(queries, dbs, pairs=None, mode: Mode = Mode.Global, *, max_steps: int = 64,
-                 max_width: int = 64, device: int = 0) -> list[tuple[str, int]]:
+                 max_width: int = 64, device: int = 0, with_results: bool = False):
     """The reference's stdout per pair of a batch (saln_wfa_render_batch: one
     GPU run, every pair computed once): [(text, status)] in pair order
-    (pairs=None: all-vs-all, db outer / query inner, main.rs:61-62)."""
+    (pairs=None: all-vs-all, db outer / query inner, main.rs:61-62).
+    with_results: also the pairs' saln_wfa_result records, as the second
+    value (structured array, as wfa_align_batch returns)."""
     qs, qo = pack_csr(queries)
     ds, do = pack_csr(dbs)
     if pairs is None:
@@ -72,13 +74,15 @@ def render_batch(queries, dbs, pairs=None, mode: Mode = Mode.Global, *, max_step
                "saln_wfa_render_batch")
     try:
         out = []
-        for k in range(L.saln_wfa_text_count(h)):
+        recs = np.zeros(L.saln_wfa_text_count(h), dtype=_lib.WFA_RESULT_DTYPE)
+        for k in range(len(recs)):
             tp, tn, res = C.c_void_p(), C.c_uint64(), _lib.WfaResult()
             _lib.check(L.saln_wfa_text_get(h, k, C.byref(tp), C.byref(tn), C.byref(res)),
                        "saln_wfa_text_get")
             out.append((C.string_at(tp.value, tn.value).decode("latin-1") if tn.value else "",
                         res.status))
-        return out
+            recs[k:k + 1] = np.frombuffer(bytes(res), dtype=_lib.WFA_RESULT_DTYPE)
+        return (out, recs) if with_results else out
     finally:
         L.saln_wfa_text_free(h)
 
