@@ -11,11 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "saln.h"
-
-namespace saln {
-void set_error(const std::string &msg);
-}
+#include "host_common.hpp"
 
 struct saln_records {
     std::vector<std::vector<uint8_t>> names, seqs;

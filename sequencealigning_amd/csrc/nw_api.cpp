@@ -2,7 +2,6 @@
 // host batch, reference-text rendering and dense-mask export.  Each one is a
 // thin wrapper: upload -> plan -> saln_nw_execute (GPU) -> download.
 #include <hip/hip_runtime.h>
-#include <sys/mman.h>
 
 #include <algorithm>
 #include <atomic>
@@ -10,7 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -24,33 +23,46 @@ using namespace saln;
 
 namespace {
 
-// a context-cached device block (saln::dev_alloc), released on scope exit
-struct DevBuf {
-    saln_context *ctx;
-    void *p = nullptr;
-    explicit DevBuf(saln_context *c) : ctx(c) {}
-    ~DevBuf() {
-        if (p) {
-            (void)hipDeviceSynchronize();
-            dev_free(ctx, p);
-        }
-    }
-    hipError_t alloc(size_t n) { return dev_alloc(ctx, &p, n); }
-};
-
-#define TRY_HIP(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-            return SALN_E_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
-
 struct PlanGuard {
     saln_nw_plan *p = nullptr;
     ~PlanGuard() { saln_nw_plan_destroy(p); }
 };
+
+// Packs every pair's CIGAR densely on the device (pair k's words at doff[k],
+// from the downloaded results' lengths) and brings the used words to the
+// host: into *vec when given, else through the context's pinned staging,
+// taken under *stage_lk, which the caller holds until it has read *words.
+int fetch_cigars(saln_context *ctx, const DevBuf &dr, const DevBuf &dc,
+                 const std::vector<uint64_t> &coff, const saln_nw_result *res, uint64_t n_pairs,
+                 std::vector<uint64_t> *doff, std::vector<uint32_t> *vec,
+                 std::unique_lock<std::mutex> *stage_lk, const uint32_t **words) {
+    doff->assign(n_pairs + 1, 0);
+    for (uint64_t k = 0; k < n_pairs; ++k) (*doff)[k + 1] = (*doff)[k] + res[k].cigar_len;
+    const uint64_t used = (*doff)[n_pairs];
+    if (vec) vec->resize(used);
+    *words = vec ? vec->data() : nullptr;
+    if (!used) return SALN_OK;
+    DevBuf dso(ctx), ddo(ctx), dcd(ctx);
+    HIP_TRY(dso.alloc((n_pairs + 1) * 8));
+    HIP_TRY(ddo.alloc((n_pairs + 1) * 8));
+    HIP_TRY(dcd.alloc(used * 4));
+    HIP_TRY(hipMemcpy(dso.p, coff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ddo.p, doff->data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(launch_cigar_compact(dr.as<saln_nw_result>(), dso.as<uint64_t>(), ddo.as<uint64_t>(),
+                                 dc.as<uint32_t>(), dcd.as<uint32_t>(), n_pairs, ctx->stream));
+    if (vec) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(vec->data(), dcd.p, used * 4, hipMemcpyDeviceToHost));
+        return SALN_OK;
+    }
+    void *st = nullptr;
+    stage_lk->lock();
+    HIP_TRY(pinned_staging(ctx, used * 4, &st));
+    HIP_TRY(hipMemcpyAsync(st, dcd.p, used * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *words = (const uint32_t *)st;
+    return SALN_OK;
+}
 
 }  // namespace
 
@@ -68,8 +80,8 @@ static int run_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_
     // plan is host work: descriptors, order, layout), joined before execute
     DevBuf dq(ctx), dd(ctx), dr(ctx), dc(ctx);
     const uint64_t qbytes = q_off[n_q], dbytes = db_off[n_db];
-    TRY_HIP(dq.alloc(qbytes));
-    TRY_HIP(dd.alloc(dbytes));
+    HIP_TRY(dq.alloc(qbytes));
+    HIP_TRY(dd.alloc(dbytes));
     hipError_t up_err = hipSuccess;
     const bool upload = mode == SALN_MODE_GLOBAL;  // other modes: every pair "not implemented"
     std::thread up([&] {
@@ -97,63 +109,33 @@ static int run_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_
     std::vector<uint64_t> coff(n_pairs + 1);
     saln_nw_cigar_offsets(g.p, coff.data());
     uint64_t cig_words = coff[n_pairs];
-    TRY_HIP(dr.alloc(n_pairs * sizeof(saln_nw_result)));
-    TRY_HIP(dc.alloc(cig_words * 4));
+    HIP_TRY(dr.alloc(n_pairs * sizeof(saln_nw_result)));
+    HIP_TRY(dc.alloc(cig_words * 4));
     up.join();
-    TRY_HIP(up_err);
+    HIP_TRY(up_err);
     clk.mark("alloc+h2d");
-    rc = saln_nw_execute(g.p, (const uint8_t *)dq.p, (const uint8_t *)dd.p,
-                         (saln_nw_result *)dr.p, (uint32_t *)dc.p, nullptr);
+    rc = saln_nw_execute(g.p, dq.as<uint8_t>(), dd.as<uint8_t>(), dr.as<saln_nw_result>(),
+                         dc.as<uint32_t>(), nullptr);
     if (rc != SALN_OK) return rc;
-    TRY_HIP(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     if ((rc = plan_check_error(g.p)) != SALN_OK) return rc;
     clk.mark("execute");
-    TRY_HIP(hipMemcpy(results, dr.p, n_pairs * sizeof(saln_nw_result), hipMemcpyDeviceToHost));
-    // CIGARs: packed densely on the device, one download of the used words
-    // into pinned staging, scattered to the caller's offsets
-    std::vector<uint64_t> doff(n_pairs + 1, 0);
-    for (uint64_t k = 0; k < n_pairs; ++k) doff[k + 1] = doff[k] + results[k].cigar_len;
+    HIP_TRY(hipMemcpy(results, dr.p, n_pairs * sizeof(saln_nw_result), hipMemcpyDeviceToHost));
+    // CIGARs: one download of the used words into pinned staging (held until
+    // the scatter below has read it), scattered to the caller's offsets
+    std::vector<uint64_t> doff;
     const uint32_t *hc = nullptr;
-    DevBuf dso(ctx), ddo(ctx), dcd(ctx);
-    // the context's pinned staging: held until the scatter below has read it
     std::unique_lock<std::mutex> stage_lk(ctx->staging_mu, std::defer_lock);
-    if (cigar && doff[n_pairs]) {
-        TRY_HIP(dso.alloc((n_pairs + 1) * 8));
-        TRY_HIP(ddo.alloc((n_pairs + 1) * 8));
-        TRY_HIP(dcd.alloc(doff[n_pairs] * 4));
-        TRY_HIP(hipMemcpy(dso.p, coff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice));
-        TRY_HIP(hipMemcpy(ddo.p, doff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice));
-        TRY_HIP(launch_cigar_compact((const saln_nw_result *)dr.p, (const uint64_t *)dso.p,
-                                     (const uint64_t *)ddo.p, (const uint32_t *)dc.p,
-                                     (uint32_t *)dcd.p, n_pairs, ctx->stream));
-        void *st = nullptr;
-        stage_lk.lock();
-        TRY_HIP(pinned_staging(ctx, doff[n_pairs] * 4, &st));
-        TRY_HIP(hipMemcpyAsync(st, dcd.p, doff[n_pairs] * 4, hipMemcpyDeviceToHost, ctx->stream));
-        TRY_HIP(hipStreamSynchronize(ctx->stream));
-        hc = (const uint32_t *)st;
-    }
+    if (cigar && (rc = fetch_cigars(ctx, dr, dc, coff, results, n_pairs, &doff, nullptr, &stage_lk,
+                                    &hc)) != SALN_OK)
+        return rc;
     clk.mark("d2h");
-    if (cigar && hc) {
-        // ~10^5 small copies (a few hundred bytes each): split over host threads
-        auto scatter = [&](uint64_t a, uint64_t b) {
-            for (uint64_t k = a; k < b; ++k) {
-                const uint64_t dst = cigar_off ? cigar_off[k] : coff[k];
-                std::memcpy(cigar + dst, hc + doff[k], results[k].cigar_len * 4);
-            }
-        };
-        const uint64_t nt = std::min<uint64_t>(
-            std::max(1u, std::min(16u, std::thread::hardware_concurrency())), n_pairs / 4096 + 1);
-        if (nt <= 1) {
-            scatter(0, n_pairs);
-        } else {
-            std::vector<std::thread> th;
-            for (uint64_t t = 1; t < nt; ++t)
-                th.emplace_back(scatter, n_pairs * t / nt, n_pairs * (t + 1) / nt);
-            scatter(0, n_pairs / nt);
-            for (auto &x : th) x.join();
-        }
-    }
+    // ~10^5 small copies (a few hundred bytes each): split over host threads
+    if (hc)
+        host_parallel(n_pairs, 4096, n_pairs / 4096 + 1, [&](uint64_t k) {
+            const uint64_t dst = cigar_off ? cigar_off[k] : coff[k];
+            std::memcpy(cigar + dst, hc + doff[k], results[k].cigar_len * 4);
+        });
     clk.mark("scatter");
     // callers that render reference text get every pair's full parent codes
     if (masks_out) {
@@ -251,24 +233,6 @@ void block_from_cigar(const uint8_t *q, const uint8_t *d, const uint32_t *w, uin
     }
 }
 
-// work items [0, n) on up to 16 host threads, handed out in blocks of `grain`
-void host_parallel(uint64_t n, uint64_t grain, const std::function<void(uint64_t)> &f) {
-    const uint64_t nt = std::min<uint64_t>(std::max(1u, std::min(16u, std::thread::hardware_concurrency())),
-                                           n / grain + 1);
-    std::atomic<uint64_t> next{0};
-    auto work = [&]() {
-        for (;;) {
-            const uint64_t b = next.fetch_add(grain);
-            if (b >= n) return;
-            for (uint64_t k = b; k < std::min(n, b + grain); ++k) f(k);
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint64_t i = 1; i < nt; ++i) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
-
 }  // namespace
 
 int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
@@ -279,7 +243,7 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     if (!ctx || !q_off || !db_off || !out) return SALN_E_INVALID;
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    auto *t = new saln_nw_text;
+    auto t = std::make_unique<saln_nw_text>();
     t->text.resize(n_pairs);
     t->blocks.assign(n_pairs, 0);
     t->ns.assign(n_pairs, 0);
@@ -291,71 +255,49 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
             t->res[k].status = t->status[k] = SALN_NOT_IMPLEMENTED;
         }
         t->count = n_pairs;
-        *out = t;
+        *out = t.release();
         return SALN_OK;
     }
     PlanGuard g;
     int rc = plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, mode, nullptr,
                          true, &g.p);
-    if (rc != SALN_OK) {
-        delete t;
-        return rc;
-    }
+    if (rc != SALN_OK) return rc;
     StageClock clock(ctx->opts.effective());
     auto fail = [&](hipError_t e, const char *what) {
         set_error(std::string(what) + ": " + hipGetErrorString(e));
-        delete t;
         return SALN_E_HIP;
     };
-    std::vector<uint64_t> coff(n_pairs + 1), doff(n_pairs + 1, 0);
+    std::vector<uint64_t> coff(n_pairs + 1), doff;
     std::vector<uint32_t> hcig;    // every pair's first alignment, packed (doff)
     std::vector<uint8_t> next(n_pairs, kNextHost);
     {
-        DevBuf dq(ctx), dd(ctx), dr(ctx), dc(ctx), dnx(ctx), dso(ctx), ddo(ctx), dcd(ctx);
-        const uint64_t qbytes = q_off[n_q], dbytes = db_off[n_db];
+        DevBuf dq(ctx), dd(ctx), dr(ctx), dc(ctx), dnx(ctx);
         saln_nw_cigar_offsets(g.p, coff.data());
         hipError_t e;
-        if ((e = dq.alloc(qbytes)) != hipSuccess || (e = dd.alloc(dbytes)) != hipSuccess ||
-            (e = dr.alloc(n_pairs * sizeof(saln_nw_result))) != hipSuccess ||
+        if ((e = upload_seqs(dq, dd, q_seq, q_off, n_q, db_seq, db_off, n_db, 0)) != hipSuccess)
+            return fail(e, "render batch: upload");
+        if ((e = dr.alloc(n_pairs * sizeof(saln_nw_result))) != hipSuccess ||
             (e = dc.alloc(std::max<uint64_t>(1, coff[n_pairs]) * 4)) != hipSuccess ||
             (e = dnx.alloc(std::max<uint64_t>(1, n_pairs))) != hipSuccess)
             return fail(e, "render batch: device buffers");
-        if ((qbytes && (e = hipMemcpy(dq.p, q_seq, qbytes, hipMemcpyHostToDevice)) != hipSuccess) ||
-            (dbytes && (e = hipMemcpy(dd.p, db_seq, dbytes, hipMemcpyHostToDevice)) != hipSuccess))
-            return fail(e, "render batch: upload");
         clock.mark("render: plan + upload");
-        rc = saln_nw_execute(g.p, (const uint8_t *)dq.p, (const uint8_t *)dd.p,
-                             (saln_nw_result *)dr.p, (uint32_t *)dc.p, ctx->stream);
+        rc = saln_nw_execute(g.p, dq.as<uint8_t>(), dd.as<uint8_t>(), dr.as<saln_nw_result>(),
+                             dc.as<uint32_t>(), ctx->stream);
         if (rc == SALN_OK)
-            rc = plan_next_event(g.p, (const saln_nw_result *)dr.p, (uint8_t *)dnx.p, ctx->stream);
+            rc = plan_next_event(g.p, dr.as<saln_nw_result>(), dnx.as<uint8_t>(), ctx->stream);
         if (rc == SALN_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
             return fail(e, "execute");
         clock.mark("render: execute");
         if (rc == SALN_OK) rc = plan_check_error(g.p);
-        if (rc != SALN_OK) {
-            delete t;
-            return rc;
-        }
+        if (rc != SALN_OK) return rc;
         if (n_pairs && ((e = hipMemcpy(t->res.data(), dr.p, n_pairs * sizeof(saln_nw_result),
                                        hipMemcpyDeviceToHost)) != hipSuccess ||
                         (e = hipMemcpy(next.data(), dnx.p, n_pairs, hipMemcpyDeviceToHost)) != hipSuccess))
             return fail(e, "render batch: results");
-        // first alignments: packed densely on the device, one download
-        for (uint64_t k = 0; k < n_pairs; ++k) doff[k + 1] = doff[k] + t->res[k].cigar_len;
-        hcig.resize(doff[n_pairs]);
-        if (doff[n_pairs]) {
-            if ((e = dso.alloc((n_pairs + 1) * 8)) != hipSuccess ||
-                (e = ddo.alloc((n_pairs + 1) * 8)) != hipSuccess ||
-                (e = dcd.alloc(doff[n_pairs] * 4)) != hipSuccess ||
-                (e = hipMemcpy(dso.p, coff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(ddo.p, doff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = launch_cigar_compact((const saln_nw_result *)dr.p, (const uint64_t *)dso.p,
-                                          (const uint64_t *)ddo.p, (const uint32_t *)dc.p,
-                                          (uint32_t *)dcd.p, n_pairs, ctx->stream)) != hipSuccess ||
-                (e = hipStreamSynchronize(ctx->stream)) != hipSuccess ||
-                (e = hipMemcpy(hcig.data(), dcd.p, doff[n_pairs] * 4, hipMemcpyDeviceToHost)) != hipSuccess)
-                return fail(e, "render batch: alignments");
-        }
+        // first alignments: one download straight into hcig
+        const uint32_t *words = nullptr;
+        rc = fetch_cigars(ctx, dr, dc, coff, t->res.data(), n_pairs, &doff, &hcig, nullptr, &words);
+        if (rc != SALN_OK) return rc;
     }
     clock.mark("render: results");
     // with stop_at_panic, pairs after the first panicking one are never
@@ -396,7 +338,7 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     t->aoff.assign(n_pairs, saln_nw_text::kNoArena);
     t->alen.assign(n_pairs, 0);
     std::vector<uint64_t> cols(nd);
-    host_parallel(nd, 1024, [&](uint64_t x) {
+    host_parallel(nd, 1024, nd / 1024 + 1, [&](uint64_t x) {
         const uint64_t k = dec[x];
         cols[x] = cigar_columns(hcig.data() + doff[k], t->res[k].cigar_len);
     });
@@ -407,22 +349,17 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         t->alen[k] = kBlockFixed + 3 * cols[x];
         asz += t->alen[k];
     }
-    if (asz) {
-        constexpr size_t kHuge = size_t(2) << 20;
-        const size_t want = (asz + kHuge - 1) / kHuge * kHuge;
-        void *hp = nullptr;
-        if (posix_memalign(&hp, kHuge, want) != 0 || !hp) {
-            set_error("render batch: text buffer allocation failed");
-            delete t;
-            return SALN_E_HIP;
-        }
-        (void)madvise(hp, want, MADV_HUGEPAGE);  // advisory: fewer first-touch faults
-        t->arena = (char *)hp;
+    size_t got = 0;
+    if (asz && !(t->arena = (char *)huge_alloc(asz, &got))) {
+        set_error("render batch: text buffer allocation failed");
+        return SALN_E_HIP;
     }
-    host_parallel(nd, 256, [&](uint64_t x) {
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};  // (the plan has checked every pair)
+    host_parallel(nd, 256, nd / 256 + 1, [&](uint64_t x) {
         const uint64_t k = dec[x];
         const auto a = std::chrono::steady_clock::now();
-        const uint64_t qi = pair_q ? pair_q[k] : k % n_q, di = pair_db ? pair_db[k] : k / n_q;
+        uint64_t qi, di;
+        (void)pairs.at(k, &qi, &di);
         block_from_cigar(q_seq + q_off[qi], db_seq + db_off[di], hcig.data() + doff[k],
                          t->res[k].cigar_len, cols[x], t->arena + t->aoff[k]);
         t->ns[k] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -434,10 +371,7 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         // streamed in slices while the DFS threads render the pairs in the
         // order their bytes arrive (the download and the host work overlap)
         const uint8_t *d_mask = nullptr;
-        if ((rc = plan_mask_source(g.p, &d_mask)) != SALN_OK) {
-            delete t;
-            return rc;
-        }
+        if ((rc = plan_mask_source(g.p, &d_mask)) != SALN_OK) return rc;
         const uint64_t nh = host.size();
         std::vector<uint64_t> endb(nh);
         uint64_t total = 0;
@@ -465,19 +399,12 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         };  // (hb frees whichever buffer it holds last)
         if (total > hb.n) {
             std::free(hb.p);
-            hb.p = nullptr;
             hb.n = 0;
-            constexpr size_t kHuge = size_t(2) << 20;
-            const size_t want = (total + kHuge - 1) / kHuge * kHuge;
-            void *hp = nullptr;
-            if (posix_memalign(&hp, kHuge, want) != 0 || !hp) {
+            if (!(hb.p = (uint8_t *)huge_alloc(total, &got))) {
                 set_error("render batch: host mask buffer allocation failed");
-                delete t;
                 return SALN_E_HIP;
             }
-            (void)madvise(hp, want, MADV_HUGEPAGE);  // advisory: 4 KB pages if THP is off
-            hb.p = (uint8_t *)hp;
-            hb.n = want;
+            hb.n = got;
         }
         uint8_t *hbuf = hb.p;
         constexpr uint64_t kSlice = 32ull << 20;
@@ -494,38 +421,29 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         });
         // per-pair DFS on host threads (its cost varies by orders of magnitude
         // with the number of co-optimal paths: pairs are handed out one by one)
-        std::atomic<uint64_t> nxt{0};
-        auto work = [&]() {
-            for (;;) {
-                const uint64_t x = nxt.fetch_add(1);
-                if (x >= nh) return;
-                const uint64_t k = host[order[x]];
-                while (have.load(std::memory_order_acquire) < endb[order[x]]) {
-                    if (dl_err.load(std::memory_order_acquire)) return;
-                    std::this_thread::yield();
-                }
-                const auto a = std::chrono::steady_clock::now();
-                const uint64_t qi = pair_q ? pair_q[k] : k % n_q, di = pair_db ? pair_db[k] : k / n_q;
-                const HostMask hm = plan_host_mask(g.p, hbuf, k);
-                const DfsOutcome o = render_blocks(hm, q_seq + q_off[qi], db_seq + db_off[di],
-                                                   max_blocks, &t->text[k]);
-                t->blocks[k] = o.blocks;
-                t->status[k] = o.status;
-                t->ns[k] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                               std::chrono::steady_clock::now() - a).count();
+        host_parallel(nh, 1, nh / 64 + 1, [&](uint64_t x) {
+            const uint64_t k = host[order[x]];
+            while (have.load(std::memory_order_acquire) < endb[order[x]]) {
+                // (a failed download: this pair is skipped, and so is every
+                // later one as it is handed out; the error is reported below)
+                if (dl_err.load(std::memory_order_acquire)) return;
+                std::this_thread::yield();
             }
-        };
-        const uint64_t nt = std::min<uint64_t>(std::max(1u, std::min(16u, std::thread::hardware_concurrency())),
-                                               nh / 64 + 1);
-        std::vector<std::thread> th;
-        for (uint64_t i = 1; i < nt; ++i) th.emplace_back(work);
-        work();
-        for (auto &x : th) x.join();
+            const auto a = std::chrono::steady_clock::now();
+            uint64_t qi, di;
+            (void)pairs.at(k, &qi, &di);
+            const HostMask hm = plan_host_mask(g.p, hbuf, k);
+            const DfsOutcome o = render_blocks(hm, q_seq + q_off[qi], db_seq + db_off[di],
+                                               max_blocks, &t->text[k]);
+            t->blocks[k] = o.blocks;
+            t->status[k] = o.status;
+            t->ns[k] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+                           std::chrono::steady_clock::now() - a).count();
+        });
         dl.join();
         give_back();
         if (const int e = dl_err.load()) {
             set_error(std::string("render batch: mask download: ") + hipGetErrorString((hipError_t)e));
-            delete t;
             return SALN_E_HIP;
         }
     }
@@ -534,7 +452,7 @@ int saln_nw_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     for (uint64_t k = 0; k < n; ++k) t->ns[k] += (uint64_t)(dev_ns / (double)std::max<uint64_t>(1, n_pairs));
     t->gpu_decided = n - host.size();
     t->count = n;
-    *out = t;
+    *out = t.release();
     return SALN_OK;
 }
 

@@ -24,43 +24,35 @@ struct saln_nw_avsa {
     struct Class {
         int variant = 0;
         uint32_t nq = 0;
-        uint32_t *d_qids = nullptr;
+        DevBuf d_qids;
     };
     saln_context *ctx = nullptr;
     Options opts{};  // the context's effective options at creation
     Scoring sc{};
     uint64_t n_q = 0, n_db = 0, cells = 0;
-    uint64_t *d_qoff = nullptr, *d_doff = nullptr;
+    DevBuf d_qoff, d_doff;
     std::vector<Class> classes;
     uint32_t ld_max = 0;
-    uint32_t *d_dids = nullptr;  // non-empty db records, longest first
+    DevBuf d_dids;  // non-empty db records, longest first
     uint32_t n_dn = 0;
-    uint32_t *d_zero_q = nullptr, *d_zero_d = nullptr;
+    DevBuf d_zero_q, d_zero_d;
     uint32_t n_zq = 0, n_zd = 0;
     saln_nw_plan *fb = nullptr;  // fallback queries x non-empty db
-    uint32_t *d_fb_qids = nullptr;
+    DevBuf d_fb_qids;
     uint32_t n_fb = 0;
-    saln_nw_result *d_fb_res = nullptr;
+    DevBuf d_fb_res;
     uint64_t q_bytes = 0, d_bytes = 0;  // sequence bytes (the ACGT check)
-    uint32_t *d_generic = nullptr;      // 1: a byte outside A, C, G, T (no profiles)
+    DevBuf d_generic;                   // 1: a byte outside A, C, G, T (no profiles)
 
-    ~saln_nw_avsa() {
-        if (fb) saln_nw_plan_destroy(fb);
-        for (auto &c : classes) (void)hipFree(c.d_qids);
-        for (void *ptr : {(void *)d_qoff, (void *)d_doff, (void *)d_dids, (void *)d_zero_q,
-                          (void *)d_zero_d, (void *)d_fb_qids, (void *)d_fb_res,
-                          (void *)d_generic})
-            if (ptr) (void)hipFree(ptr);
-    }
+    ~saln_nw_avsa() { saln_nw_plan_destroy(fb); }
 };
 
 template <typename T>
-static hipError_t upload(T **dst, const std::vector<T> &v) {
-    *dst = nullptr;
+static hipError_t upload(DevBuf &dst, const std::vector<T> &v) {
     if (v.empty()) return hipSuccess;
-    hipError_t e = hipMalloc(dst, v.size() * sizeof(T));
+    hipError_t e = dst.alloc(v.size() * sizeof(T));
     if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return hipMemcpy(dst.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 extern "C" {
@@ -128,16 +120,16 @@ int saln_nw_avsa_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     a->cells = sum_q * sum_d;
     a->q_bytes = q_off[n_q];
     a->d_bytes = db_off[n_db];
-    HIP_TRY(hipMalloc(&a->d_generic, sizeof(uint32_t)));
+    HIP_TRY(a->d_generic.alloc(sizeof(uint32_t)));
     std::vector<uint64_t> qo(q_off, q_off + n_q + 1), dof(db_off, db_off + n_db + 1);
-    HIP_TRY(upload(&a->d_qoff, qo));
-    HIP_TRY(upload(&a->d_doff, dof));
+    HIP_TRY(upload(a->d_qoff, qo));
+    HIP_TRY(upload(a->d_doff, dof));
     a->n_dn = (uint32_t)dn.size();
-    HIP_TRY(upload(&a->d_dids, dn));
+    HIP_TRY(upload(a->d_dids, dn));
     a->n_zq = (uint32_t)zq.size();
     a->n_zd = (uint32_t)zd.size();
-    HIP_TRY(upload(&a->d_zero_q, zq));
-    HIP_TRY(upload(&a->d_zero_d, zd));
+    HIP_TRY(upload(a->d_zero_q, zq));
+    HIP_TRY(upload(a->d_zero_d, zd));
     for (int v = 0; v < kNumVariants; ++v) {
         if (cls[v].empty() || dn.empty()) continue;
         auto &c = cls[v];
@@ -147,8 +139,8 @@ int saln_nw_avsa_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
         saln_nw_avsa::Class k;
         k.variant = v;
         k.nq = (uint32_t)c.size();
-        HIP_TRY(upload(&k.d_qids, c));
-        a->classes.push_back(k);
+        HIP_TRY(upload(k.d_qids, c));
+        a->classes.push_back(std::move(k));
     }
     if (!fbq.empty() && !dn.empty()) {
         const uint64_t n = (uint64_t)fbq.size() * dn.size();
@@ -166,8 +158,8 @@ int saln_nw_avsa_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
         if (rc != SALN_OK) return rc;
         saln_nw_plan_set_score_only(a->fb, 1);
         a->n_fb = (uint32_t)fbq.size();
-        HIP_TRY(upload(&a->d_fb_qids, fbq));
-        HIP_TRY(hipMalloc(&a->d_fb_res, n * sizeof(saln_nw_result)));
+        HIP_TRY(upload(a->d_fb_qids, fbq));
+        HIP_TRY(a->d_fb_res.alloc(n * sizeof(saln_nw_result)));
     }
     *out = a.release();
     return SALN_OK;
@@ -181,6 +173,9 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
     hipStream_t s = resolve_stream(stream, a->ctx);
     int2 *out = reinterpret_cast<int2 *>(d_out);
     const uint32_t nqt = (uint32_t)a->n_q;
+    const uint64_t *qoff = a->d_qoff.as<uint64_t>(), *doff = a->d_doff.as<uint64_t>();
+    const uint32_t *dids = a->d_dids.as<uint32_t>();
+    uint32_t *d_generic = a->d_generic.as<uint32_t>();
     // the 8 x 19 class runs with query profiles when every byte is A, C, G
     // or T: checked here on the device, read by the kernel (no host sync)
     const bool prof = a->opts[Opt::AvsaProfile] != 0 && a->n_dn >= 2 &&
@@ -188,11 +183,11 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
                                   [](const saln_nw_avsa::Class &c) { return c.variant == 4; });
     // the other classes take table penalties under the same check (nw.pk_tab)
     const bool checked = prof || a->opts[Opt::PkTab] != 0;
-    const uint32_t *generic = checked ? a->d_generic : nullptr;
+    const uint32_t *generic = checked ? d_generic : nullptr;
     if (checked) {
-        HIP_TRY(hipMemsetAsync(a->d_generic, 0, sizeof(uint32_t), s));
-        HIP_TRY(launch_acgt_check(d_q_seq, a->q_bytes, a->d_generic, s));
-        HIP_TRY(launch_acgt_check(d_db_seq, a->d_bytes, a->d_generic, s));
+        HIP_TRY(hipMemsetAsync(d_generic, 0, sizeof(uint32_t), s));
+        HIP_TRY(launch_acgt_check(d_q_seq, a->q_bytes, d_generic, s));
+        HIP_TRY(launch_acgt_check(d_db_seq, a->d_bytes, d_generic, s));
     }
     for (const auto &c : a->classes) {
         // pairs per launch: the dispatch packet's grid size is a 32-bit count
@@ -206,14 +201,14 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
             hipError_t e = hipSuccess;
             for (uint64_t base = 0; base < tp && e == hipSuccess; base += kChunk) {
                 const uint32_t n = (uint32_t)std::min<uint64_t>(kChunk, tp - base);
-                e = launch_avsa_prof(a->d_qoff, a->d_doff, c.d_qids, c.nq, a->d_dids, nqt, base, n,
-                                     d_q_seq, d_db_seq, out, a->sc, a->ld_max, a->d_generic, s,
+                e = launch_avsa_prof(qoff, doff, c.d_qids.as<uint32_t>(), c.nq, dids, nqt, base, n,
+                                     d_q_seq, d_db_seq, out, a->sc, a->ld_max, d_generic, s,
                                      a->opts);
             }
             if (e == hipSuccess) {
                 if (a->n_dn & 1u)
-                    HIP_TRY(launch_avsa(c.variant, a->d_qoff, a->d_doff, c.d_qids, c.nq,
-                                        a->d_dids + (a->n_dn - 1), nqt, 0, c.nq, d_q_seq, d_db_seq,
+                    HIP_TRY(launch_avsa(c.variant, qoff, doff, c.d_qids.as<uint32_t>(), c.nq,
+                                        dids + (a->n_dn - 1), nqt, 0, c.nq, d_q_seq, d_db_seq,
                                         out, a->sc, a->ld_max, s, a->opts, generic));
                 continue;
             }
@@ -222,23 +217,23 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
         }
         for (uint64_t base = 0; base < total; base += kChunk) {
             const uint32_t n = (uint32_t)std::min<uint64_t>(kChunk, total - base);
-            HIP_TRY(launch_avsa(c.variant, a->d_qoff, a->d_doff, c.d_qids, c.nq, a->d_dids, nqt,
+            HIP_TRY(launch_avsa(c.variant, qoff, doff, c.d_qids.as<uint32_t>(), c.nq, dids, nqt,
                                 base, n, d_q_seq, d_db_seq, out, a->sc, a->ld_max, s, a->opts,
                                 generic));
         }
     }
     // empty db records x every query; empty queries x non-empty db records
-    HIP_TRY(launch_avsa_boundary(a->d_qoff, a->d_doff, nullptr, nqt, a->d_zero_d,
+    HIP_TRY(launch_avsa_boundary(qoff, doff, nullptr, nqt, a->d_zero_d.as<uint32_t>(),
                                  (uint64_t)nqt * a->n_zd, nqt, out, a->sc, s));
-    HIP_TRY(launch_avsa_boundary(a->d_qoff, a->d_doff, a->d_zero_q, a->n_zq, a->d_dids,
+    HIP_TRY(launch_avsa_boundary(qoff, doff, a->d_zero_q.as<uint32_t>(), a->n_zq, dids,
                                  (uint64_t)a->n_zq * a->n_dn, nqt, out, a->sc, s));
     if (a->fb) {
         // the caller's stream argument as given: `s` is the resolved handle,
         // and a resolved legacy null stream (0) would read as "the context's
         // own stream" there, unordered with the scatter below
-        const int rc = saln_nw_execute(a->fb, d_q_seq, d_db_seq, a->d_fb_res, nullptr, stream);
+        const int rc = saln_nw_execute(a->fb, d_q_seq, d_db_seq, a->d_fb_res.as<saln_nw_result>(), nullptr, stream);
         if (rc != SALN_OK) return rc;
-        HIP_TRY(launch_avsa_scatter(a->d_fb_res, a->d_fb_qids, a->n_fb, a->d_dids,
+        HIP_TRY(launch_avsa_scatter(a->d_fb_res.as<saln_nw_result>(), a->d_fb_qids.as<uint32_t>(), a->n_fb, dids,
                                     (uint64_t)a->n_fb * a->n_dn, nqt, out, s));
     }
     return SALN_OK;

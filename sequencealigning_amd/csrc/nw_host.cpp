@@ -18,14 +18,9 @@
 #include <unordered_set>
 #include <vector>
 
-#include <sys/mman.h>
-
 #include "nw_host.hpp"
 
 namespace saln {
-
-static thread_local std::string g_err;
-void set_error(const std::string &msg) { g_err = msg; }
 
 Scoring scoring_or_default(const saln_nw_scoring *s) {
     if (!s) return Scoring{5, -4, -8, -6};  // SCHEME, needleman_wunsch_affine.rs:15-20
@@ -133,7 +128,6 @@ struct saln_nw_plan {
 
 extern "C" {
 
-const char *saln_last_error(void) { return g_err.c_str(); }
 int saln_abi_version(void) { return SALN_ABI_VERSION; }
 
 int saln_context_create(int device, saln_context **out) {
@@ -147,11 +141,9 @@ int saln_context_create(int device, saln_context **out) {
     std::thread pre_th;
     if (const int64_t mb = opt(Opt::HostPrefaultMb); mb > 0) {
         pre_th = std::thread([&pre, mb] {
-            constexpr size_t kHuge = size_t(2) << 20;
-            const size_t want = (((size_t)mb << 20) + kHuge - 1) / kHuge * kHuge;
-            void *hp = nullptr;
-            if (posix_memalign(&hp, kHuge, want) != 0 || !hp) return;
-            (void)madvise(hp, want, MADV_HUGEPAGE);
+            size_t want = 0;
+            void *hp = huge_alloc((size_t)mb << 20, &want);
+            if (!hp) return;
             std::memset(hp, 0, want);
             pre.p = (uint8_t *)hp;
             pre.n = want;
@@ -304,12 +296,8 @@ int saln::plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
         set_error("not implemented");  // needleman_wunsch_affine.rs:433-434
         return SALN_NOT_IMPLEMENTED;
     }
-    if ((pair_q == nullptr) != (pair_db == nullptr)) return SALN_E_INVALID;
-    if (!pair_q && n_pairs != n_q * n_db) {
-        set_error("all-vs-all needs n_pairs == n_q * n_db");
-        return SALN_E_INVALID;
-    }
-    if (n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
+    if (!pairs.complete(n_pairs) || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     HIP_TRY(hipSetDevice(ctx->device));
     const Options opts = ctx->opts.effective();
     StageClock clk(opts);
@@ -334,23 +322,16 @@ int saln::plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     bool memo_fit = false;
     int memo_var = 0;
     for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t qi = pair_q ? pair_q[k] : k % n_q;
-        const uint64_t di = pair_db ? pair_db[k] : k / n_q;
-        if (qi >= n_q || di >= n_db) {
+        uint64_t qi, di, lq, ld;
+        if (!pairs.at(k, &qi, &di) ||
+            !pair_lengths(q_off, db_off, qi, di, 0x7FFFFFFFull, &lq, &ld)) {
             delete p;
-            set_error("pair index out of range");
             return SALN_E_INVALID;
         }
         NwPairDesc &d = descs[k];
         std::memset(&d, 0, sizeof(d));
         d.q_off = q_off[qi];
         d.db_off = db_off[di];
-        const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        if (lq > 0x7FFFFFFFull || ld > 0x7FFFFFFFull) {
-            delete p;
-            set_error("sequence too long");
-            return SALN_E_INVALID;
-        }
         if (lq != memo_lq || ld != memo_ld) {
             memo_lq = lq;
             memo_ld = ld;
@@ -1274,72 +1255,4 @@ bool first_alignment(const HostMask &hm, const uint8_t *q, const uint8_t *d,
 
 namespace saln {
 int plan_check_error(saln_nw_plan *p) { return saln_nw_plan_status(p, nullptr); }
-}  // namespace saln
-
-namespace saln {
-
-hipError_t dev_alloc(saln_context *ctx, void **p, size_t n) {
-    n = n ? (n + 255) & ~size_t(255) : 256;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        auto it = ctx->cache.lower_bound(n);
-        if (it != ctx->cache.end() && it->first <= 2 * n) {
-            *p = it->second;
-            ctx->live[it->second] = it->first;
-            ctx->cached -= it->first;
-            ctx->cache.erase(it);
-            return hipSuccess;
-        }
-    }
-    hipError_t e = hipMalloc(p, n);
-    if (e == hipErrorOutOfMemory) {  // give the cached blocks back and retry once
-        (void)hipGetLastError();
-        dev_cache_clear(ctx);
-        e = hipMalloc(p, n);
-    }
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->live[*p] = n;
-    return hipSuccess;
-}
-
-void dev_free(saln_context *ctx, void *p) {
-    if (!p) return;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto it = ctx->live.find(p);
-    if (it == ctx->live.end()) {
-        (void)hipFree(p);
-        return;
-    }
-    const size_t n = it->second;
-    ctx->live.erase(it);
-    if (ctx->cached + n > kDevCacheMax) {
-        (void)hipFree(p);
-        return;
-    }
-    ctx->cache.emplace(n, p);
-    ctx->cached += n;
-}
-
-void dev_cache_clear(saln_context *ctx) {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    for (auto &kv : ctx->cache) (void)hipFree(kv.second);
-    ctx->cache.clear();
-    ctx->cached = 0;
-}
-
-hipError_t pinned_staging(saln_context *ctx, size_t n, void **p) {
-    if (n > ctx->pinned_bytes) {
-        const size_t want = std::max(n, ctx->pinned_bytes * 2);
-        if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-        ctx->pinned = nullptr;
-        ctx->pinned_bytes = 0;
-        hipError_t e = hipHostMalloc(&ctx->pinned, want, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        ctx->pinned_bytes = want;
-    }
-    *p = ctx->pinned;
-    return hipSuccess;
-}
-
 }  // namespace saln

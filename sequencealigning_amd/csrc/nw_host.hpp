@@ -1,88 +1,15 @@
 // Host-side pieces shared by the C ABI and the CLI.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <chrono>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <functional>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
+#include "host_common.hpp"
 #include "nw_common.hpp"
-#include "saln_options.hpp"
-#include "saln.h"
-
-struct saln_context {
-    int device = 0;
-    saln::OptOverrides opts;  // saln_context_option_set (on top of the process registry)
-    hipStream_t stream = nullptr;
-    hipStream_t tb_stream = nullptr;  // traceback stream (pipelined NW plans)
-    // Device blocks released by plans / host-path calls, kept for reuse
-    // (hipMalloc + hipFree of a 3 GB mask workspace cost more than the C2
-    // kernels): size -> block; `live` maps handed-out blocks to their size.
-    std::mutex mu;
-    std::multimap<size_t, void *> cache;
-    std::unordered_map<void *, size_t> live;
-    size_t cached = 0;
-    // pinned host staging for the host-path downloads (grow-only); staging_mu
-    // is held by a user of the buffer from its first copy to its last host
-    // read (pinned_staging may free and reallocate it when it grows)
-    std::mutex staging_mu;
-    void *pinned = nullptr;
-    size_t pinned_bytes = 0;
-    // pageable host copy of render batches' mask workspaces (grow-only,
-    // uninitialised, 2 MB-aligned with transparent huge pages requested: the
-    // first copy into 1.1 GB of 4 KB pages spent ~0.17 s in page faults; under
-    // staging_mu): pinning a GB-sized buffer costs more than the copy it
-    // speeds up (measured: 333 ms to pin, 234 ms to unpin 1.1 GB)
-    struct HostBuf {
-        uint8_t *p = nullptr;
-        size_t n = 0;
-        ~HostBuf() { std::free(p); }
-    } host_mask;
-};
-
-// A C-ABI stream argument: NULL = the context's own (non-blocking) stream;
-// hipStreamLegacy = the legacy null stream (torch's default stream), used as
-// the handle 0 that every HIP call accepts; anything else as given.
-inline hipStream_t resolve_stream(void *stream, const saln_context *ctx) {
-    if (!stream) return ctx->stream;
-    if ((hipStream_t)stream == hipStreamLegacy) return (hipStream_t)0;
-    return (hipStream_t)stream;
-}
-
 
 namespace saln {
-
-// option host.timing = 1: stage times of the host-side paths on stderr
-struct StageClock {
-    bool on;
-    explicit StageClock(const Options &o) : on(o[Opt::HostTiming] != 0) {}
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void mark(const char *what) {
-        if (!on) return;
-        (void)hipDeviceSynchronize();
-        const auto n = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[saln host] %-16s %8.3f ms\n", what,
-                     std::chrono::duration<double, std::milli>(n - t).count());
-        t = n;
-    }
-};
-
-// Context-cached device memory: a released block is reused by a later request
-// of at most twice its size; at most kDevCacheMax bytes stay cached.  A block
-// must not be released while kernels may still use it (plan destroy syncs).
-constexpr size_t kDevCacheMax = size_t(32) << 30;
-hipError_t dev_alloc(saln_context *ctx, void **p, size_t n);
-void dev_free(saln_context *ctx, void *p);
-void dev_cache_clear(saln_context *ctx);
-hipError_t pinned_staging(saln_context *ctx, size_t n, void **p);  // caller holds ctx->staging_mu
 
 // kernels (nw_kernels.hip)
 // What a packed fill launch needs besides the pairs: the plan's options, the
@@ -209,17 +136,7 @@ Geom variant_geom(int v);
 bool variant_packed(int v);
 int choose_variant(uint32_t len_q, uint32_t len_db, const Scoring &sc, bool narrow = false);
 
-void set_error(const std::string &msg);
 Scoring scoring_or_default(const saln_nw_scoring *s);
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            ::saln::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));          \
-            return SALN_E_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
 
 // Host copy of one pair's parent codes: LB-byte segments, row-major, with
 // row stride rs and block stride bs (nw_common.hpp Geom).

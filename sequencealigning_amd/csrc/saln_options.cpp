@@ -5,8 +5,7 @@
 #include <cstring>
 #include <string>
 
-#include "nw_host.hpp"
-#include "saln.h"
+#include "host_common.hpp"
 
 namespace saln {
 

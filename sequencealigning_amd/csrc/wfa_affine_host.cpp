@@ -24,10 +24,8 @@
 #include <string>
 #include <vector>
 
-#include "nw_host.hpp"
-#include "saln.h"
+#include "host_common.hpp"
 #include "wfa_affine.hpp"
-#include "saln_options.hpp"
 
 using namespace saln;
 
@@ -36,8 +34,9 @@ struct saln_wfa_affine_plan {
     WfaAffParams prm{};
     bool wide = false;  // i32 offsets (a sequence longer than 32,000 bases)
     uint64_t n = 0;
-    WfaAffPair *d_pairs = nullptr, *d_rerun = nullptr;
-    uint32_t *d_count = nullptr;  // [rerun pairs, pass-1 next pair, pass-2 next pair]
+    std::vector<WfaAffPair> pairs;  // host copy of d_pairs (alignment mode reads the lengths)
+    DevBuf d_pairs, d_rerun;
+    DevBuf d_count;  // [rerun pairs, pass-1 next pair, pass-2 next pair]
     WfaAffParams p1{}, p2{};  // the two passes (ring width, LDS sequence staging)
     uint32_t grid1 = 0, grid2 = 0;
 };
@@ -52,15 +51,6 @@ constexpr int32_t kW1 = 1024, kW2 = 2048, kW1Wide = 512, kW2Wide = 1024;
 constexpr uint64_t kLdsLimit = 64u << 10;  // dynamic LDS of one workgroup
 constexpr uint64_t kI16MaxLen = 32000;     // longest sequence of a plan with i16 offsets
 constexpr uint64_t kMaxLen = 0x3FFFFFFFull;  // longest sequence the engine takes
-
-#define TRY(expr)                                                                          \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-            return SALN_E_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
 
 int make_params(const saln_wfa_penalties *pen, int32_t max_score, WfaAffParams *out) {
     const int32_t x = pen ? pen->mismatch : 4, o = pen ? pen->gap_open : 2,
@@ -163,14 +153,15 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
                 const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
                 std::vector<WfaAffPair> *out, BatchShape *shape) {
     out->resize(n_pairs);
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
     for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t qi = pair_q ? pair_q[k] : k % n_q, di = pair_db ? pair_db[k] : k / n_q;
-        if (qi >= n_q || di >= n_db) return SALN_E_INVALID;
+        uint64_t qi, di, lq, ld;
+        if (!pairs.at(k, &qi, &di) || !pair_lengths(q_off, db_off, qi, di, kMaxLen, &lq, &ld) ||
+            !shape->add(lq, ld))
+            return SALN_E_INVALID;
         WfaAffPair p{};
         p.q_off = q_off[qi];
         p.d_off = db_off[di];
-        const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        if (!shape->add(lq, ld)) return SALN_E_INVALID;
         p.lq = (uint32_t)lq;
         p.ld = (uint32_t)ld;
         p.out = (uint32_t)k;
@@ -217,43 +208,32 @@ int saln_wfa_affine_plan_create(saln_context *ctx, const uint64_t *q_off, uint64
                                 const saln_wfa_penalties *pen, int32_t max_score,
                                 saln_wfa_affine_plan **out) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
-    if (!pair_q != !pair_db) return SALN_E_INVALID;
-    if (!pair_q && n_pairs != n_q * n_db) return SALN_E_INVALID;
-    auto *p = new saln_wfa_affine_plan();
+    if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
+    auto p = std::make_unique<saln_wfa_affine_plan>();
     p->ctx = ctx;
     int rc = make_params(pen, max_score, &p->prm);
-    std::vector<WfaAffPair> hp;
     BatchShape shape;
-    if (rc == SALN_OK) rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &shape);
+    if (rc == SALN_OK)
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &p->pairs, &shape);
     p->wide = shape.wide();
     // the passes before anything touches the device: a refused ring width or
     // penalty set never reaches an allocation or a launch
     if (rc == SALN_OK)
         rc = plan_passes(p->prm, p->wide, shape.seq_need, shape.code_need,
                          ctx->opts.effective(), &p->p1, &p->p2);
-    if (rc != SALN_OK) {
-        delete p;
-        return rc;
-    }
+    if (rc != SALN_OK) return rc;
     p->n = n_pairs;
-    auto fail = [&](hipError_t e) {
-        set_error(std::string("wfa_affine plan: ") + hipGetErrorString(e));
-        saln_wfa_affine_plan_destroy(p);
-        return SALN_E_HIP;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(ctx->device)) != hipSuccess) return fail(e);
+    HIP_TRY(hipSetDevice(ctx->device));
     if (n_pairs) {
-        if ((e = hipMalloc(&p->d_pairs, n_pairs * sizeof(WfaAffPair))) != hipSuccess) return fail(e);
-        if ((e = hipMalloc(&p->d_rerun, n_pairs * sizeof(WfaAffPair))) != hipSuccess) return fail(e);
-        if ((e = hipMalloc(&p->d_count, 3 * sizeof(uint32_t))) != hipSuccess) return fail(e);
-        if ((e = hipMemcpy(p->d_pairs, hp.data(), n_pairs * sizeof(WfaAffPair),
-                           hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(e);
+        HIP_TRY(p->d_pairs.alloc(n_pairs * sizeof(WfaAffPair)));
+        HIP_TRY(p->d_rerun.alloc(n_pairs * sizeof(WfaAffPair)));
+        HIP_TRY(p->d_count.alloc(3 * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(p->d_pairs.p, p->pairs.data(), n_pairs * sizeof(WfaAffPair),
+                          hipMemcpyHostToDevice));
     }
     p->grid1 = grid_for(p->p1, p->wide, n_pairs, ctx->device);
     p->grid2 = grid_for(p->p2, p->wide, n_pairs, ctx->device);
-    *out = p;
+    *out = p.release();
     return SALN_OK;
 }
 
@@ -262,23 +242,48 @@ int saln_wfa_affine_execute(saln_wfa_affine_plan *p, const uint8_t *d_q_seq,
     if (!p || !d_scores || !d_q_seq || !d_db_seq) return SALN_E_INVALID;
     if (!p->n) return SALN_OK;
     hipStream_t s = resolve_stream(stream, p->ctx);
-    TRY(hipSetDevice(p->ctx->device));
-    TRY(hipMemsetAsync(p->d_count, 0, 3 * sizeof(uint32_t), s));
-    TRY(launch_wfa_affine(p->d_pairs, (uint32_t)p->n, d_q_seq, d_db_seq, p->p1, p->wide, p->grid1,
-                          nullptr, p->d_count + 1, d_scores, s));
-    TRY(launch_wfa_affine_compact(p->d_pairs, (uint32_t)p->n, d_scores, p->d_rerun, p->d_count, s));
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    WfaAffPair *pairs = p->d_pairs.as<WfaAffPair>(), *rerun = p->d_rerun.as<WfaAffPair>();
+    uint32_t *count = p->d_count.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(count, 0, 3 * sizeof(uint32_t), s));
+    HIP_TRY(launch_wfa_affine(pairs, (uint32_t)p->n, d_q_seq, d_db_seq, p->p1, p->wide, p->grid1,
+                              nullptr, count + 1, d_scores, s));
+    HIP_TRY(launch_wfa_affine_compact(pairs, (uint32_t)p->n, d_scores, rerun, count, s));
     // pass 2 reads its pair count from the device (no host round trip)
-    TRY(launch_wfa_affine(p->d_rerun, (uint32_t)p->n, d_q_seq, d_db_seq, p->p2, p->wide, p->grid2,
-                          p->d_count, p->d_count + 2, d_scores, s));
+    HIP_TRY(launch_wfa_affine(rerun, (uint32_t)p->n, d_q_seq, d_db_seq, p->p2, p->wide, p->grid2,
+                              count, count + 2, d_scores, s));
     return SALN_OK;
 }
 
 int saln_wfa_affine_plan_destroy(saln_wfa_affine_plan *p) {
-    if (!p) return SALN_OK;
-    if (p->d_pairs) (void)hipFree(p->d_pairs);
-    if (p->d_rerun) (void)hipFree(p->d_rerun);
-    if (p->d_count) (void)hipFree(p->d_count);
     delete p;
+    return SALN_OK;
+}
+
+// The score passes of a host batch: the plan, both sequence sets on the
+// device with 16 bytes of padding (in dq / dd, whose allocator the scores'
+// block shares) and every pair's score on the host.  A sequence longer than
+// len_limit is refused before anything runs.
+static int score_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                       uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
+                       const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
+                       const saln_wfa_penalties *pen, int32_t max_score, uint32_t len_limit,
+                       DevBuf &dq, DevBuf &dd, std::unique_ptr<saln_wfa_affine_plan> *plan,
+                       int32_t *scores) {
+    saln_wfa_affine_plan *p = nullptr;
+    int rc = saln_wfa_affine_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs,
+                                         pen, max_score, &p);
+    if (rc != SALN_OK) return rc;
+    plan->reset(p);
+    for (const WfaAffPair &k : p->pairs)
+        if (k.lq > len_limit || k.ld > len_limit) return SALN_E_INVALID;
+    DevBuf dsc = dq.sibling();
+    HIP_TRY(upload_seqs(dq, dd, q_seq, q_off, n_q, db_seq, db_off, n_db, 16));
+    HIP_TRY(dsc.alloc(std::max<size_t>(n_pairs * sizeof(int32_t), 16)));
+    rc = saln_wfa_affine_execute(p, dq.as<uint8_t>(), dd.as<uint8_t>(), dsc.as<int32_t>(), nullptr);
+    if (rc != SALN_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(scores, dsc.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
     return SALN_OK;
 }
 
@@ -289,34 +294,10 @@ int saln_wfa_affine_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_
                           int32_t *scores) {
     if (!ctx || !q_off || !db_off || !scores) return SALN_E_INVALID;
     if (n_pairs == 0) return SALN_OK;
-    saln_wfa_affine_plan *plan = nullptr;
-    int rc = saln_wfa_affine_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs,
-                                         pen, max_score, &plan);
-    if (rc != SALN_OK) return rc;
-    struct Guard {
-        saln_wfa_affine_plan *p;
-        std::vector<void *> bufs;
-        ~Guard() {
-            for (void *b : bufs) (void)hipFree(b);
-            saln_wfa_affine_plan_destroy(p);
-        }
-    } g{plan, {}};
-    const uint64_t qb = q_off[n_q], db = db_off[n_db];
-    void *dq = nullptr, *dd = nullptr, *dsc = nullptr;
-    TRY(hipMalloc(&dq, qb + 16));
-    g.bufs.push_back(dq);
-    TRY(hipMalloc(&dd, db + 16));
-    g.bufs.push_back(dd);
-    TRY(hipMalloc(&dsc, n_pairs * sizeof(int32_t)));
-    g.bufs.push_back(dsc);
-    if (qb) TRY(hipMemcpy(dq, q_seq, qb, hipMemcpyHostToDevice));
-    if (db) TRY(hipMemcpy(dd, db_seq, db, hipMemcpyHostToDevice));
-    rc = saln_wfa_affine_execute(plan, (const uint8_t *)dq, (const uint8_t *)dd, (int32_t *)dsc,
-                                 nullptr);
-    if (rc != SALN_OK) return rc;
-    TRY(hipStreamSynchronize(ctx->stream));
-    TRY(hipMemcpy(scores, dsc, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return SALN_OK;
+    std::unique_ptr<saln_wfa_affine_plan> plan;
+    DevBuf dq, dd;
+    return score_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, pen,
+                       max_score, (uint32_t)kMaxLen, dq, dd, &plan, scores);
 }
 
 int saln_wfa_affine_trace_bytes(const saln_wfa_penalties *pen, uint64_t len_q, uint64_t len_db,
@@ -365,49 +346,18 @@ int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const u
         *out = aln.release();
         return SALN_OK;
     }
-    // the score passes (saln_wfa_affine_batch's plan), sequences kept on the device
-    saln_wfa_affine_plan *plan = nullptr;
-    int rc = saln_wfa_affine_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs,
-                                         pen, max_score, &plan);
+    // the score passes (saln_wfa_affine_batch's), sequences kept on the device
+    // in blocks of the context's cache; a CIGAR run holds 2^28-1 columns
+    std::unique_ptr<saln_wfa_affine_plan> plan;
+    hipStream_t s = ctx->stream;  // every launch below runs on it: the blocks sync it alone
+    DevBuf dq(ctx, s), dd(ctx, s);
+    std::vector<int32_t> scores(n_pairs);
+    int rc = score_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs,
+                         pen, max_score, 0x0FFFFFFFu, dq, dd, &plan, scores.data());
     if (rc != SALN_OK) return rc;
     aln->res.assign(n_pairs, saln_wfa_affine_result{});
     aln->off.assign(n_pairs + 1, 0);
-    struct Guard {
-        saln_context *ctx;
-        saln_wfa_affine_plan *p;
-        std::vector<void *> bufs;
-        ~Guard() {
-            (void)hipStreamSynchronize(ctx->stream);
-            for (void *b : bufs) dev_free(ctx, b);
-            saln_wfa_affine_plan_destroy(p);
-        }
-    } g{ctx, plan, {}};
-    auto alloc = [&](void **p, size_t n) {
-        const hipError_t e = dev_alloc(ctx, p, std::max<size_t>(n, 16));
-        if (e == hipSuccess) g.bufs.push_back(*p);
-        return e;
-    };
-    std::vector<WfaAffPair> hp;
-    {
-        BatchShape shape;
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, &hp, &shape);
-        if (rc != SALN_OK) return rc;
-    }
-    for (const WfaAffPair &p : hp)  // a CIGAR run holds 2^28-1 columns
-        if (p.lq > 0x0FFFFFFFu || p.ld > 0x0FFFFFFFu) return SALN_E_INVALID;
-    const uint64_t qb = q_off[n_q], db = db_off[n_db];
-    void *dq = nullptr, *dd = nullptr, *dsc = nullptr;
-    TRY(alloc(&dq, qb + 16));
-    TRY(alloc(&dd, db + 16));
-    TRY(alloc(&dsc, n_pairs * sizeof(int32_t)));
-    if (qb) TRY(hipMemcpy(dq, q_seq, qb, hipMemcpyHostToDevice));
-    if (db) TRY(hipMemcpy(dd, db_seq, db, hipMemcpyHostToDevice));
-    rc = saln_wfa_affine_execute(plan, (const uint8_t *)dq, (const uint8_t *)dd, (int32_t *)dsc,
-                                 nullptr);
-    if (rc != SALN_OK) return rc;
-    TRY(hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> scores(n_pairs);
-    TRY(hipMemcpy(scores.data(), dsc, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const std::vector<WfaAffPair> &hp = plan->pairs;
 
     // chunks: pairs in pair order, at most `budget` bytes of trace workspace each
     const uint64_t budget = trace_budget_bytes ? trace_budget_bytes : (1ull << 30);
@@ -449,15 +399,16 @@ int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const u
         max_words = std::max(max_words, c.words);
         max_n = std::max<uint64_t>(max_n, c.tp.size());
     }
-    void *d_tp = nullptr, *d_codes = nullptr, *d_words = nullptr, *d_status = nullptr,
-         *d_len = nullptr, *d_next = nullptr;
+    DevBuf d_tp(ctx, s), d_codes(ctx, s), d_words(ctx, s), d_status(ctx, s), d_len(ctx, s),
+        d_next(ctx, s);
     if (!chunks.empty()) {
-        TRY(alloc(&d_tp, max_n * sizeof(WfaAffTracePair)));
-        TRY(alloc(&d_codes, max_bytes));
-        TRY(alloc(&d_words, max_words * sizeof(uint32_t)));
-        TRY(alloc(&d_status, max_n * sizeof(int32_t)));
-        TRY(alloc(&d_len, max_n * sizeof(uint32_t)));
-        TRY(alloc(&d_next, 2 * sizeof(uint32_t)));
+        const auto min16 = [](size_t n) { return std::max<size_t>(n, 16); };
+        HIP_TRY(d_tp.alloc(min16(max_n * sizeof(WfaAffTracePair))));
+        HIP_TRY(d_codes.alloc(min16(max_bytes)));
+        HIP_TRY(d_words.alloc(min16(max_words * sizeof(uint32_t))));
+        HIP_TRY(d_status.alloc(min16(max_n * sizeof(int32_t))));
+        HIP_TRY(d_len.alloc(min16(max_n * sizeof(uint32_t))));
+        HIP_TRY(d_next.alloc(min16(2 * sizeof(uint32_t))));
     }
     // Per chunk: the fill with the first ring over every pair, the fill with
     // the second ring over the pairs the first left (kTraceRerun in their
@@ -466,7 +417,6 @@ int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const u
     std::vector<uint64_t> ids;
     std::vector<int32_t> h_status;
     std::vector<uint32_t> h_len, h_words;
-    hipStream_t s = ctx->stream;
     uint64_t next_pair = 0;  // pairs before it have their offset
     for (Chunk &c : chunks) {
         const uint32_t n = (uint32_t)c.tp.size();
@@ -475,29 +425,28 @@ int saln_wfa_affine_align_batch(saln_context *ctx, const uint8_t *q_seq, const u
             ids[i] = c.tp[i].p.out;
             c.tp[i].p.out = i;
         }
-        TRY(hipMemcpy(d_tp, c.tp.data(), n * sizeof(WfaAffTracePair), hipMemcpyHostToDevice));
-        TRY(hipMemsetAsync(d_next, 0, 2 * sizeof(uint32_t), s));
-        const auto *dp = (const WfaAffTracePair *)d_tp;
-        TRY(launch_wfa_affine_trace(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, plan->p1,
-                                    plan->wide, /*rerun=*/false,
-                                    grid_for(plan->p1, plan->wide, n, ctx->device),
-                                    (uint32_t *)d_next, (uint8_t *)d_codes, (int32_t *)d_status, s));
-        TRY(launch_wfa_affine_trace(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, plan->p2,
-                                    plan->wide, /*rerun=*/true,
-                                    grid_for(plan->p2, plan->wide, n, ctx->device),
-                                    (uint32_t *)d_next + 1, (uint8_t *)d_codes,
-                                    (int32_t *)d_status, s));
-        TRY(launch_wfa_affine_walk(dp, n, (const uint8_t *)dq, (const uint8_t *)dd, prm,
-                                   (uint8_t *)d_codes, (int32_t *)d_status, (uint32_t *)d_words,
-                                   (uint32_t *)d_len, s));
-        TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(d_tp.p, c.tp.data(), n * sizeof(WfaAffTracePair), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(d_next.p, 0, 2 * sizeof(uint32_t), s));
+        const auto *dp = d_tp.as<const WfaAffTracePair>();
+        const uint8_t *sq = dq.as<uint8_t>(), *sd = dd.as<uint8_t>();
+        uint8_t *codes = d_codes.as<uint8_t>();
+        int32_t *status = d_status.as<int32_t>();
+        HIP_TRY(launch_wfa_affine_trace(dp, n, sq, sd, plan->p1, plan->wide, /*rerun=*/false,
+                                        grid_for(plan->p1, plan->wide, n, ctx->device),
+                                        d_next.as<uint32_t>(), codes, status, s));
+        HIP_TRY(launch_wfa_affine_trace(dp, n, sq, sd, plan->p2, plan->wide, /*rerun=*/true,
+                                        grid_for(plan->p2, plan->wide, n, ctx->device),
+                                        d_next.as<uint32_t>() + 1, codes, status, s));
+        HIP_TRY(launch_wfa_affine_walk(dp, n, sq, sd, prm, codes, status, d_words.as<uint32_t>(),
+                                       d_len.as<uint32_t>(), s));
+        HIP_TRY(hipStreamSynchronize(s));
         h_status.resize(n);
         h_len.resize(n);
         h_words.resize(c.words);
-        TRY(hipMemcpy(h_status.data(), d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        TRY(hipMemcpy(h_len.data(), d_len, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        TRY(hipMemcpy(h_words.data(), d_words, c.words * sizeof(uint32_t),
-                      hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_status.data(), status, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_len.data(), d_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_words.data(), d_words.p, c.words * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; ++i) {
             saln_wfa_affine_result &r = aln->res[ids[i]];
             r.status = h_status[i] == SALN_OK ? SALN_OK : SALN_INTERNAL;

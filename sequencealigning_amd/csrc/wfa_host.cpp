@@ -7,38 +7,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "nw_host.hpp"
+#include "host_common.hpp"
 #include "wfa_host.hpp"
 
 using namespace saln;
 
 namespace {
-
-#define TRY_HIP(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-            return SALN_E_HIP;                                                             \
-        }                                                                                  \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
 
 constexpr uint32_t kDefaultSteps = 64, kDefaultWidth = 64;
 // Tensor history per launch: "wfa.arena_mb" (default 32 GB, sized for 288 GB of
@@ -85,10 +66,7 @@ struct WfaScratch {
         nl_ = std::min<uint64_t>(nl_, n_pairs);
         if (S_ * nl_ > S * nl || S_ * W_ * nl_ > S * W * nl) {
             for (;;) {  // out of memory: halve the lanes per launch (down to 256)
-                for (DevBuf *b : {&hdr, &off, &meta, &tsome}) {
-                    if (b->p) (void)hipFree(b->p);
-                    b->p = nullptr;
-                }
+                for (DevBuf *b : {&hdr, &off, &meta, &tsome}) b->reset();
                 S = W = nl = 0;
                 hipError_t e;
                 if ((e = hdr.alloc(S_ * 3 * 4 * nl_ * sizeof(int32_t))) == hipSuccess &&
@@ -105,8 +83,8 @@ struct WfaScratch {
             nl = nl_;
         }
         // the kernel indexes with the launch's own (S, W, nl) inside the buffers
-        *out = WfaArena{(int32_t *)hdr.p, (int32_t *)off.p, (uint32_t *)meta.p,
-                        (uint8_t *)tsome.p, (uint32_t)nl_, (uint32_t)S_, (uint32_t)W_};
+        *out = WfaArena{hdr.as<int32_t>(), off.as<int32_t>(), meta.as<uint32_t>(),
+                        tsome.as<uint8_t>(), (uint32_t)nl_, (uint32_t)S_, (uint32_t)W_};
         return hipSuccess;
     }
 };
@@ -117,10 +95,10 @@ int wfa_pass(WfaScratch &ws, const WfaPairDesc *d_pairs, uint32_t n, const uint8
              uint8_t *d_aln, int32_t *d_lohi, uint8_t *d_ev, uint32_t ev_cap, WfaPairDesc *rerun,
              uint32_t *rerun_cnt, hipStream_t s) {
     WfaArena arena;
-    TRY_HIP(ws.arena(steps / 2 + 1, width, n, &arena));
+    HIP_TRY(ws.arena(steps / 2 + 1, width, n, &arena));
     for (uint64_t first = 0; first < n; first += arena.nl) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(arena.nl, n - first);
-        TRY_HIP(launch_wfa(d_pairs, (uint32_t)first, cnt, dq, dd, arena, steps, d_res, d_aln,
+        HIP_TRY(launch_wfa(d_pairs, (uint32_t)first, cnt, dq, dd, arena, steps, d_res, d_aln,
                            d_lohi, d_ev, ev_cap, rerun, rerun_cnt, s));
     }
     return SALN_OK;
@@ -138,22 +116,20 @@ int wfa_device(WfaScratch &ws, const WfaPairDesc *d_pairs, uint32_t n, const uin
         return wfa_pass(ws, d_pairs, n, dq, dd, max_steps, width, d_res, d_aln, d_lohi, d_ev,
                         ev_cap, nullptr, nullptr, s);
     if (ws.rerun_n < n) {
-        if (ws.rerun.p) (void)hipFree(ws.rerun.p);
-        ws.rerun.p = nullptr;
-        TRY_HIP(ws.rerun.alloc((uint64_t)n * sizeof(WfaPairDesc)));
+        HIP_TRY(ws.rerun.alloc((uint64_t)n * sizeof(WfaPairDesc)));
         ws.rerun_n = n;
     }
-    if (!ws.cnt.p) TRY_HIP(ws.cnt.alloc(sizeof(uint32_t)));
-    TRY_HIP(hipMemsetAsync(ws.cnt.p, 0, sizeof(uint32_t), s));
+    if (!ws.cnt.p) HIP_TRY(ws.cnt.alloc(sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(ws.cnt.p, 0, sizeof(uint32_t), s));
     int rc = wfa_pass(ws, d_pairs, n, dq, dd, kFirstPassSteps, width, d_res, d_aln, nullptr,
-                      nullptr, 0, (WfaPairDesc *)ws.rerun.p, (uint32_t *)ws.cnt.p, s);
+                      nullptr, 0, ws.rerun.as<WfaPairDesc>(), ws.cnt.as<uint32_t>(), s);
     if (rc != SALN_OK) return rc;
     uint32_t again = 0;
-    TRY_HIP(hipMemcpyAsync(&again, ws.cnt.p, sizeof again, hipMemcpyDeviceToHost, s));
-    TRY_HIP(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(&again, ws.cnt.p, sizeof again, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     if (!again) return SALN_OK;
-    return wfa_pass(ws, (const WfaPairDesc *)ws.rerun.p, again, dq, dd, max_steps, width, d_res,
-                    d_aln, nullptr, nullptr, 0, nullptr, nullptr, s);
+    return wfa_pass(ws, ws.rerun.as<WfaPairDesc>(), again, dq, dd, max_steps, width, d_res, d_aln,
+                    nullptr, nullptr, 0, nullptr, nullptr, s);
 }
 
 int build_descs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
@@ -162,22 +138,16 @@ int build_descs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
                 uint64_t *aln_bytes) {
     out->resize(n_pairs);
     *aln_bytes = 0;
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
     for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t qi = pair_q ? pair_q[k] : k % n_q;
-        const uint64_t di = pair_db ? pair_db[k] : k / n_q;
-        if (qi >= n_q || di >= n_db) {
-            set_error("pair index out of range");
+        uint64_t qi, di, lq, ld;
+        if (!pairs.at(k, &qi, &di) ||
+            !pair_lengths(q_off, db_off, qi, di, 0x7FFFFFFFull, &lq, &ld))
             return SALN_E_INVALID;
-        }
         WfaPairDesc &d = (*out)[k];
         std::memset(&d, 0, sizeof d);
         d.q_off = q_off[qi];
         d.db_off = db_off[di];
-        const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        if (lq > 0x7FFFFFFFull || ld > 0x7FFFFFFFull) {
-            set_error("sequence too long");
-            return SALN_E_INVALID;
-        }
         d.len_q = (uint32_t)lq;
         d.len_db = (uint32_t)ld;
         d.pair_id = (uint32_t)k;
@@ -201,43 +171,39 @@ int run_wfa(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint
     if (!max_width) max_width = kDefaultWidth;
     if (n_pairs == 0) return SALN_OK;
     if (n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
-    TRY_HIP(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     std::vector<WfaPairDesc> descs;
     uint64_t aln_bytes = 0;
     int rc = build_descs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, mode, aln_off,
                          aln ? aln_cap : 0, &descs, &aln_bytes);
     if (rc != SALN_OK) return rc;
-    const uint64_t qbytes = q_off[n_q], dbytes = db_off[n_db];
     DevBuf dq, dd, dp, dr, da, dl, de;
-    TRY_HIP(dq.alloc(qbytes));
-    TRY_HIP(dd.alloc(dbytes));
-    TRY_HIP(dp.alloc(n_pairs * sizeof(WfaPairDesc)));
-    TRY_HIP(dr.alloc(n_pairs * sizeof(saln_wfa_result)));
-    if (qbytes) TRY_HIP(hipMemcpy(dq.p, q_seq, qbytes, hipMemcpyHostToDevice));
-    if (dbytes) TRY_HIP(hipMemcpy(dd.p, db_seq, dbytes, hipMemcpyHostToDevice));
-    TRY_HIP(hipMemcpy(dp.p, descs.data(), n_pairs * sizeof(WfaPairDesc), hipMemcpyHostToDevice));
-    if (aln) TRY_HIP(da.alloc(aln_bytes));
+    HIP_TRY(upload_seqs(dq, dd, q_seq, q_off, n_q, db_seq, db_off, n_db, 0));
+    HIP_TRY(dp.alloc(n_pairs * sizeof(WfaPairDesc)));
+    HIP_TRY(dr.alloc(n_pairs * sizeof(saln_wfa_result)));
+    HIP_TRY(hipMemcpy(dp.p, descs.data(), n_pairs * sizeof(WfaPairDesc), hipMemcpyHostToDevice));
+    if (aln) HIP_TRY(da.alloc(aln_bytes));
     const uint32_t ev_cap = ev_cap_for(max_steps);
     if (logs) {
-        TRY_HIP(dl.alloc(n_pairs * 2ull * max_steps * sizeof(int32_t)));
-        TRY_HIP(de.alloc(n_pairs * (uint64_t)ev_cap));
+        HIP_TRY(dl.alloc(n_pairs * 2ull * max_steps * sizeof(int32_t)));
+        HIP_TRY(de.alloc(n_pairs * (uint64_t)ev_cap));
     }
     WfaScratch ws;
     ws.budget_bytes = arena_budget(ctx);
-    rc = wfa_device(ws, (const WfaPairDesc *)dp.p, (uint32_t)n_pairs, (const uint8_t *)dq.p,
-                    (const uint8_t *)dd.p, max_steps, max_width, (saln_wfa_result *)dr.p,
-                    (uint8_t *)da.p, (int32_t *)dl.p, (uint8_t *)de.p, ev_cap, ctx->stream);
+    rc = wfa_device(ws, dp.as<WfaPairDesc>(), (uint32_t)n_pairs, dq.as<uint8_t>(), dd.as<uint8_t>(),
+                    max_steps, max_width, dr.as<saln_wfa_result>(), da.as<uint8_t>(),
+                    dl.as<int32_t>(), de.as<uint8_t>(), ev_cap, ctx->stream);
     if (rc != SALN_OK) return rc;
-    TRY_HIP(hipStreamSynchronize(ctx->stream));
-    TRY_HIP(hipMemcpy(results, dr.p, n_pairs * sizeof(saln_wfa_result), hipMemcpyDeviceToHost));
-    if (aln) TRY_HIP(hipMemcpy(aln, da.p, aln_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(results, dr.p, n_pairs * sizeof(saln_wfa_result), hipMemcpyDeviceToHost));
+    if (aln) HIP_TRY(hipMemcpy(aln, da.p, aln_bytes, hipMemcpyDeviceToHost));
     if (logs) {
         logs->lohi.resize(n_pairs * 2ull * max_steps);
         logs->ev.resize(n_pairs * (uint64_t)ev_cap);
         logs->ev_cap = ev_cap;
-        TRY_HIP(hipMemcpy(logs->lohi.data(), dl.p, logs->lohi.size() * sizeof(int32_t),
+        HIP_TRY(hipMemcpy(logs->lohi.data(), dl.p, logs->lohi.size() * sizeof(int32_t),
                           hipMemcpyDeviceToHost));
-        TRY_HIP(hipMemcpy(logs->ev.data(), de.p, logs->ev.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(logs->ev.data(), de.p, logs->ev.size(), hipMemcpyDeviceToHost));
     }
     return SALN_OK;
 }
@@ -416,16 +382,15 @@ int saln_wfa_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_
     }
     std::vector<uint32_t> pq(n_pairs), pd(n_pairs);
     std::vector<uint64_t> acap_k(n_pairs);
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
     for (uint64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t qi = pair_q ? pair_q[k] : k % std::max<uint64_t>(n_q, 1);
-        const uint64_t di = pair_db ? pair_db[k] : k / std::max<uint64_t>(n_q, 1);
-        if (qi >= n_q || di >= n_db) {
-            set_error("pair index out of range");
+        uint64_t qi, di, lq, ld;
+        if (!pairs.at(k, &qi, &di) ||
+            !pair_lengths(q_off, db_off, qi, di, 0x7FFFFFFFull, &lq, &ld))
             return SALN_E_INVALID;
-        }
         pq[k] = (uint32_t)qi;
         pd[k] = (uint32_t)di;
-        acap_k[k] = 2 * ((q_off[qi + 1] - q_off[qi]) + (db_off[di + 1] - db_off[di])) + 64;
+        acap_k[k] = 2 * (lq + ld) + 64;
         if (acap_k[k] > 0x7FFFFFFF) {
             set_error("saln_wfa_render_batch: sequence too long");
             return SALN_E_INVALID;
@@ -436,7 +401,6 @@ int saln_wfa_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_
     // kChunkBytes; each chunk is one GPU run
     constexpr uint64_t kChunkBytes = 1ull << 30;
     const uint64_t per_log = 2ull * max_steps * sizeof(int32_t) + ev_cap_for(max_steps);
-    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     for (uint64_t c0 = 0; c0 < n_pairs;) {
         uint64_t acap = 64, c1 = c0;
         while (c1 < n_pairs) {
@@ -454,23 +418,15 @@ int saln_wfa_render_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_
                          pd.data() + c0, n, mode, max_steps, max_width, t->res.data() + c0,
                          aln.data(), aoff.data(), (uint32_t)acap, &logs);
         if (rc != SALN_OK) return rc;
-        const unsigned nth = (unsigned)std::min<uint64_t>(hw, (n + 63) / 64);
-        std::atomic<uint64_t> next{0};
-        auto work = [&] {
-            for (uint64_t k; (k = next.fetch_add(1)) < n;) {
-                const uint64_t g = c0 + k;
-                const uint8_t *al = aln.data() + aoff[k];
-                const long long diag = (long long)(q_off[pq[g] + 1] - q_off[pq[g]]) -
-                                       (long long)(db_off[pd[g] + 1] - db_off[pd[g]]);
-                render_pair(t->res[g], logs.lohi.data() + k * 2 * max_steps,
-                            logs.ev.data() + k * logs.ev_cap, logs.ev_cap, al, al + acap,
-                            (uint32_t)acap, diag, &t->text[g]);
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned i = 1; i < nth; ++i) th.emplace_back(work);
-        work();
-        for (auto &x : th) x.join();
+        host_parallel(n, 1, (n + 63) / 64, [&](uint64_t k) {
+            const uint64_t g = c0 + k;
+            const uint8_t *al = aln.data() + aoff[k];
+            const long long diag = (long long)(q_off[pq[g] + 1] - q_off[pq[g]]) -
+                                   (long long)(db_off[pd[g] + 1] - db_off[pd[g]]);
+            render_pair(t->res[g], logs.lohi.data() + k * 2 * max_steps,
+                        logs.ev.data() + k * logs.ev_cap, logs.ev_cap, al, al + acap,
+                        (uint32_t)acap, diag, &t->text[g]);
+        });
         c0 = c1;
     }
     *out = t.release();
@@ -497,7 +453,7 @@ int saln_wfa_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     if (!ctx || !q_off || !db_off || !out) return SALN_E_INVALID;
     *out = nullptr;
     if (n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
-    TRY_HIP(hipSetDevice(ctx->device));
+    HIP_TRY(hipSetDevice(ctx->device));
     auto p = std::make_unique<saln_wfa_plan>();
     p->ctx = ctx;
     p->n_pairs = (uint32_t)n_pairs;
@@ -510,8 +466,8 @@ int saln_wfa_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
                          &descs, &ab);
     if (rc != SALN_OK) return rc;
     if (n_pairs) {
-        TRY_HIP(p->pairs.alloc(n_pairs * sizeof(WfaPairDesc)));
-        TRY_HIP(hipMemcpy(p->pairs.p, descs.data(), n_pairs * sizeof(WfaPairDesc),
+        HIP_TRY(p->pairs.alloc(n_pairs * sizeof(WfaPairDesc)));
+        HIP_TRY(hipMemcpy(p->pairs.p, descs.data(), n_pairs * sizeof(WfaPairDesc),
                           hipMemcpyHostToDevice));
     }
     *out = p.release();
@@ -521,9 +477,9 @@ int saln_wfa_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
 int saln_wfa_execute(saln_wfa_plan *p, const uint8_t *d_q_seq, const uint8_t *d_db_seq,
                      saln_wfa_result *d_results, void *stream) {
     if (!p || (p->n_pairs && (!d_q_seq || !d_db_seq || !d_results))) return SALN_E_INVALID;
-    TRY_HIP(hipSetDevice(p->ctx->device));
+    HIP_TRY(hipSetDevice(p->ctx->device));
     hipStream_t s = resolve_stream(stream, p->ctx);
-    return wfa_device(p->ws, (const WfaPairDesc *)p->pairs.p, p->n_pairs, d_q_seq, d_db_seq,
+    return wfa_device(p->ws, p->pairs.as<WfaPairDesc>(), p->n_pairs, d_q_seq, d_db_seq,
                       p->max_steps, p->max_width, d_results, nullptr, nullptr, nullptr, 0, s);
 }
 

@@ -19,7 +19,7 @@
 
 #include <cstdint>
 
-#include "nw_host.hpp"
+#include "host_common.hpp"
 #include "saln.h"
 #include "wfa_host.hpp"
 
