@@ -72,11 +72,10 @@ typedef enum {
  * The scheme only selects the kernel (packed int16 where the range guards
  * hold, int32 otherwise), never the result: the reference recurrences' with
  * these four values.  Checked against the CPU oracle for match and mismatch
- * of either sign and relative order, gap_open of either sign and
- * gap_extend <= 0; a positive gap_extend is accepted but
- * covered by no test.  A pair so long, or penalties so large, that its
- * scores could leave the engine's int32 range is refused with SALN_E_INVALID
- * by every entry point. */
+ * of either sign and relative order, and gap_open and gap_extend of either
+ * sign (a positive gap_extend runs on the int32 kernels).  A
+ * pair so long, or penalties so large, that its scores could leave the
+ * engine's int32 range is refused with SALN_E_INVALID by every entry point. */
 typedef struct {
     int32_t match;      /* +5 */
     int32_t mismatch;   /* -4 */
@@ -271,7 +270,9 @@ int saln_nw_plan_create_full(saln_context *ctx, const uint64_t *q_off, uint64_t 
                              const saln_nw_scoring *scoring, saln_nw_plan **out);
 /* Pair `pair`'s parent sets from the last execute of a synchronous full plan
  * (waits for it), as saln_nw_dense_mask lays them out: (len_db+1) x (len_q+1)
- * bytes. */
+ * bytes.  SALN_E_INVALID while the plan is score-only
+ * (saln_nw_plan_set_score_only(plan, 1)): such executes store no codes, and
+ * the workspace holds whatever an earlier execute left. */
 int saln_nw_plan_dense_mask(saln_nw_plan *plan, uint64_t pair, uint8_t *out);
 /* The 4-bit walk codes a (non-full) plan's short-query fills store for pair
  * `pair` (parity tests): len_db x len_q bytes, cell (i, j) at (i-1) len_q +
@@ -279,7 +280,8 @@ int saln_nw_plan_dense_mask(saln_nw_plan *plan, uint64_t pair, uint8_t *out);
  * I / D in max(M, I, D) at (i, j), :120-153), 2 I-open (M(i, j) + open
  * among the maxima of I(i, j+1), :108-119), 3 D-open (the same for D(i+1,
  * j), :96-107); in the last row bit 3 of the end cell is argM.  Last
- * synchronous execute; SALN_E_INVALID for a pair stored otherwise. */
+ * synchronous execute; SALN_E_INVALID for a pair stored otherwise, and
+ * for every pair while the plan is score-only (its executes store no codes). */
 int saln_nw_plan_walk_codes(saln_nw_plan *plan, uint64_t pair, uint8_t *out);
 /* mask_bytes: HBM parent-mask workspace (owned by the plan);
  * cigar_words: required length of the device cigar buffer. */

@@ -234,6 +234,10 @@ int saln_nw_plan_dense_mask(saln_nw_plan *p, uint64_t pair, uint8_t *out) {
         set_error("saln_nw_plan_dense_mask: synchronous plans only");
         return SALN_E_INVALID;
     }
+    if (p->score_only) {  // the fills of a score-only execute store no codes
+        set_error("saln_nw_plan_dense_mask: the plan is score-only (set_score_only(0) and execute first)");
+        return SALN_E_INVALID;
+    }
     HIP_TRY(hipSetDevice(p->ctx->device));
     for (int b = 0; b < 2; ++b)
         if (p->tb_pending[b]) HIP_TRY(hipEventSynchronize(p->tb_done(b)));
@@ -250,6 +254,10 @@ int saln_nw_plan_walk_codes(saln_nw_plan *p, uint64_t pair, uint8_t *out) {
     if (!p || !out || pair >= p->n_pairs) return SALN_E_INVALID;
     if (p->async_tb) {
         set_error("saln_nw_plan_walk_codes: synchronous plans only");
+        return SALN_E_INVALID;
+    }
+    if (p->score_only) {  // the fills of a score-only execute store no codes
+        set_error("saln_nw_plan_walk_codes: the plan is score-only (set_score_only(0) and execute first)");
         return SALN_E_INVALID;
     }
     const NwPairDesc &d = p->h_pairs[p->plan_index[pair]];

@@ -1155,3 +1155,78 @@ def test_walk_codes_bit_by_bit(saln, oracle, saln_opt, tab):
         assert np.array_equal((got[:-1, :] & 8) != 0, (dm[2:, 1:] & 0x40) == 0), (k, "D-open")
         assert bool(got[ld - 1, lq - 1] & 8) == ((dm[ld, lq] & 1) == 0), (k, "argM")
     plan.close()
+
+
+def _score_only_toggle(saln, queries, dbs, full, export, want):
+    """A synchronous plan executes and export(plan, k) equals want(k); in
+    score-only mode the fills store no codes and the export refuses
+    (SALN_E_INVALID) instead of copying what the workspace still holds; back in
+    full mode and executed again, it equals want(k) again."""
+    import torch
+    from sequencealigning_amd import _lib
+    m = len(queries)
+    qcat, qo = saln.pack_csr(queries)
+    dcat, do = saln.pack_csr(dbs)
+    plan = saln.NwPlan(qo, do, pairs=np.stack([np.arange(m)] * 2, 1), full_codes=full)
+    dq, dd = torch.from_numpy(qcat.copy()).cuda(), torch.from_numpy(dcat.copy()).cuda()
+    r = torch.zeros(m * 4, dtype=torch.int32, device="cuda")
+    c = torch.zeros(max(1, plan.cigar_words), dtype=torch.int32, device="cuda")
+
+    def run():
+        plan.execute(dq, dd, r, c)
+        plan.check()
+        torch.cuda.synchronize()
+
+    run()
+    for k in range(m):
+        want(k, export(plan, k))
+    scores = r.cpu().numpy().reshape(m, 4)[:, 0].copy()
+    plan.set_score_only(True)
+    for executed in (False, True):  # refused from the switch on, not only after an execute
+        if executed:
+            run()
+            assert np.array_equal(r.cpu().numpy().reshape(m, 4)[:, 0], scores)
+        for k in range(m):
+            with pytest.raises(_lib.SalnError) as e:
+                export(plan, k)
+            assert e.value.code == _lib.E_INVALID, (k, e.value)
+            assert "score-only" in str(e.value), (k, e.value)
+    plan.set_score_only(False)
+    run()
+    for k in range(m):
+        want(k, export(plan, k))
+    plan.close()
+
+
+def test_score_only_plan_refuses_dense_mask(saln, oracle):
+    """saln_nw_plan_dense_mask once copied stale parent sets out of a
+    score-only plan with SALN_OK."""
+    rng = np.random.default_rng(911)
+    shapes = [(150, 150), (152, 300), (37, 151), (200, 180), (1, 1)]
+    queries = [rand_seq(rng, a) for a, _ in shapes]
+    dbs = [rand_seq(rng, b) for _, b in shapes]
+    masks = [oracle.nw(q, d, literal_dfs=False).dense_mask for q, d in zip(queries, dbs)]
+
+    def want(k, got):
+        assert np.array_equal(got, masks[k]), shapes[k]
+
+    _score_only_toggle(saln, queries, dbs, True, lambda p, k: p.dense_mask(k), want)
+
+
+def test_score_only_plan_refuses_walk_codes(saln, oracle):
+    """The same for saln_nw_plan_walk_codes on 150 x 150 pairs (4-bit codes)."""
+    rng = np.random.default_rng(912)
+    queries = [rand_seq(rng, 150) for _ in range(4)]
+    dbs = [rand_seq(rng, 150) for _ in range(4)]
+    masks = [oracle.nw(q, d, literal_dfs=False).dense_mask for q, d in zip(queries, dbs)]
+
+    def want(k, got):
+        dm = masks[k]
+        inner = dm[1:, 1:]
+        assert np.array_equal((got & 1) != 0, (inner & 2) == 0), (k, "argI")
+        assert np.array_equal((got & 2) != 0, (inner & 4) == 0), (k, "argD")
+        assert np.array_equal((got[:, :-1] & 4) != 0, (dm[1:, 2:] & 0x10) == 0), (k, "I-open")
+        assert np.array_equal((got[:-1, :] & 8) != 0, (dm[2:, 1:] & 0x40) == 0), (k, "D-open")
+        assert bool(got[-1, -1] & 8) == ((dm[-1, -1] & 1) == 0), (k, "argM")
+
+    _score_only_toggle(saln, queries, dbs, False, lambda p, k: p.walk_codes(k), want)

@@ -9,101 +9,11 @@ their execute will launch (NwPlan.pair_path), never by restating a guard."""
 import numpy as np
 import pytest
 
-from nw_check import SCHEMES, SENTINEL_SCHEME, expand, rand_seq
+from nw_check import (DECISIONS, KINDS, PANIC, POSITIVE_EXTEND, SCHEMES, SENTINEL_SCHEME, PlanRun, assert_batch, csr, expand,
+                      make_pair, rand_seq)
+from nw_check import scheme_seed as _seed
 
 pytestmark = pytest.mark.gpu
-
-PANIC = 2  # SALN_REF_PANIC_BOUNDARY
-KINDS = ("iid", "embedded", "disjoint", "prefix", "homopolymer")
-
-
-def make_pair(rng, kind: str, lq: int, ld: int):
-    """iid ACGT; embedded: the shorter side is a window of the longer (the
-    largest positive excursion); disjoint: q over {A, C}, d over {G, T} (all
-    mismatches, the largest negative one); prefix: the shorter side is the
-    longer one's start (the diagonal gains while column 0 drifts);
-    homopolymer: a one-letter query."""
-    if kind == "iid":
-        return rand_seq(rng, lq), rand_seq(rng, ld)
-    if kind == "disjoint":
-        return rand_seq(rng, lq, b"AC"), rand_seq(rng, ld, b"GT")
-    if kind == "homopolymer":
-        return b"A" * lq, rand_seq(rng, ld)
-    long_ = rand_seq(rng, max(lq, ld))
-    a = int(rng.integers(0, abs(lq - ld) + 1)) if kind == "embedded" else 0
-    short = long_[a:a + min(lq, ld)]
-    return (short, long_) if lq <= ld else (long_, short)
-
-
-def _seed(scheme) -> int:
-    return sum((v & 0xFFFF) << (16 * k) for k, v in enumerate(scheme))
-
-
-def csr(seqs):
-    off = np.zeros(len(seqs) + 1, np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs])
-    buf = np.frombuffer(b"".join(seqs), np.uint8) if off[-1] else np.zeros(1, np.uint8)
-    return np.ascontiguousarray(buf), off
-
-
-def assert_batch(res, cig_words, want, tag, score_only=False):
-    """res: saln_nw_result records; cig_words(k) -> pair k's CIGAR words."""
-    bad = np.flatnonzero(res["score"] != want.score)
-    assert bad.size == 0, (tag, "score", bad[:8].tolist(), res["score"][bad[:8]].tolist(),
-                           want.score[bad[:8]].tolist())
-    assert np.array_equal(res["status"] == PANIC, want.panics), (tag, "panic")
-    if score_only:
-        return
-    assert np.array_equal(res["end_states"], want.end_states), (tag, "end states")
-    assert np.array_equal(res["printed"].astype(bool), want.cig_len >= 0), (tag, "printed")
-    for k in np.flatnonzero(res["printed"]):
-        assert np.array_equal(cig_words(int(k)), want.cigar_words(int(k))), (tag, "cigar", int(k))
-
-
-class PlanRun:
-    """One plan over the k-th query against the k-th db, its device buffers,
-    and the results of its latest execute."""
-
-    def __init__(self, saln, queries, dbs, scheme, *, full=False, score_only=False, pipelined=False):
-        import torch
-        self.saln, self.n = saln, len(queries)
-        self.qs, self.qo = csr(queries)
-        self.ds, self.do = csr(dbs)
-        self.plan = saln.NwPlan(self.qo, self.do, pairs=np.stack([np.arange(self.n)] * 2, 1),
-                                scoring=scheme, full_codes=full)
-        self.score_only, self.pipelined = score_only, pipelined
-        if score_only:
-            self.plan.set_score_only(True)
-        if pipelined:
-            self.plan.set_async(True)
-        self.dq, self.dd = torch.from_numpy(self.qs.copy()).cuda(), torch.from_numpy(self.ds.copy()).cuda()
-
-    def run(self):
-        import torch
-        res_t = torch.zeros(self.n * 4, dtype=torch.int32, device="cuda")
-        cig_t = None if self.score_only else torch.zeros(max(1, self.plan.cigar_words),
-                                                         dtype=torch.int32, device="cuda")
-        self.plan.execute(self.dq, self.dd, res_t, cig_t)
-        if self.pipelined:
-            self.plan.sync()
-        torch.cuda.synchronize()
-        self.plan.check()
-        self.res = res_t.cpu().numpy().view(self.saln._lib.RESULT_DTYPE)
-        self.cig = None if cig_t is None else cig_t.cpu().numpy().view(np.uint32)
-        return self
-
-    def words(self, k):
-        o = int(self.plan.cigar_off[k])
-        return self.cig[o:o + int(self.res["cigar_len"][k])]
-
-    def close(self):
-        self.plan.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ------------------------------------------------------------- (a) variant sweep
@@ -189,16 +99,6 @@ EDGE_SCHEMES = [(5, -4, -8, -6), (2, -3, -5, -2), (8, -8, -16, -12), (12, -4, -2
                 (5, -4, -8, -20), (16, 0, -30, -40), (5, -4, -6800, -1), (8, -8, -8, -7)]
 EDGE_WIDTHS = [150, 152, 160, 256, 512, 1024]
 LD_CAP = 4096  # an edge at or beyond it is the staged-row bound, not a range guard
-# decision -> (nw.pk_tab it needs, predicate on a PairPath)
-DECISIONS = {
-    "single frame": (3, lambda p: p.packed and not p.rebase),
-    "rebasing frame": (3, lambda p: p.packed and p.rebase),
-    "table scale 2": (1, lambda p: p.table == 2),
-    "table scale 4": (2, lambda p: p.table == 4),
-    "row profiles": (3, lambda p: p.table == 3),
-}
-
-
 def _path_at(saln, scheme, lq, ld, cache):
     if ld not in cache:
         n = 64
@@ -300,7 +200,7 @@ def test_guard_edges_cover_every_decision(saln, saln_opt):
 
 # -------------------------------------------------------------------- (c) plans
 PLAN_SCHEMES = [(5, -4, -8, -6), (2, -3, -5, -2), (1, 0, 0, 0), (8, -8, -16, -12),
-                SENTINEL_SCHEME, (6, 2, -8, -6)]
+                SENTINEL_SCHEME, (6, 2, -8, -6)] + POSITIVE_EXTEND
 _ragged_cache: dict = {}
 
 
@@ -361,7 +261,8 @@ def test_ragged_plan_pipelined(saln, oracle, saln_opt, scheme, tab):
 @pytest.mark.parametrize("profile", [1, 0])
 @pytest.mark.parametrize("ld_max", [700, 500, 170])
 @pytest.mark.parametrize("scheme", [(2, -3, -5, -2), (8, -8, -16, -12), SENTINEL_SCHEME,
-                                    (8, -8, -8, -7)], ids=lambda s: "_".join(map(str, s)))
+                                    (8, -8, -8, -7)] + POSITIVE_EXTEND,
+                         ids=lambda s: "_".join(map(str, s)))
 def test_all_vs_all(saln, oracle, saln_opt, scheme, ld_max, profile):
     """64 queries x 48 dbs.  The longest db decides the classes' launches:
     700 rows keep the 16 x 10 class, 500 form the 8 x 19 class with query
@@ -416,7 +317,8 @@ def _assert_long(r, want, tag):
 
 LONG_CASES = [("mut_5000", (2, -3, -5, -2)), ("mut_5000", (1, 0, -1, 0)),
               ("iid_3000x6000", (2, -3, -5, -2)), ("iid_3000x6000", (1, 0, -1, 0)),
-              ("iid_700x650", SENTINEL_SCHEME), ("iid_2000x300", SENTINEL_SCHEME)]
+              ("iid_700x650", SENTINEL_SCHEME), ("iid_2000x300", SENTINEL_SCHEME)] + \
+    [(name, s) for s in POSITIVE_EXTEND for name in ("mut_5000", "iid_2000x300")]
 
 
 @pytest.mark.parametrize("stripes", [(1, 0), (0, 1), (0, 2)], ids=["packed", "rows_k1", "rows_k2"])
@@ -424,10 +326,17 @@ LONG_CASES = [("mut_5000", (2, -3, -5, -2)), ("mut_5000", (1, 0, -1, 0)),
 def test_long_pair_stripes(saln, oracle, saln_opt, name, scheme, stripes):
     """Column stripes: packed where the scheme allows it (nw.stripe_pk = 1),
     the row fill at one and two columns per lane, each with the speculative
-    walks on and off."""
+    walks on and off.  A positive extend has no packed stripes: forced, the
+    plan still reports the row fill, and the pair runs on it."""
     q, d, want = _long_pair(oracle, name, scheme)
     saln_opt("nw.stripe_pk", stripes[0])
     saln_opt("nw.rows_k", stripes[1])
+    if stripes[0] and scheme[3] > 0:
+        plan = saln.NwPlan(*(np.array([0, len(s)], np.uint64) for s in (q, d)), pairs=[(0, 0)],
+                           scoring=scheme)
+        path = plan.pair_path(0)
+        plan.close()
+        assert not path.packed and not path.stripe_pk, (name, scheme, path)
     for spec in (1, 0):
         saln_opt("nw.spec", spec)
         _assert_long(saln.n_w_align(q, d, scoring=scheme), want, (name, scheme, stripes, spec))

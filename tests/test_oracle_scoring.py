@@ -175,6 +175,29 @@ def test_check_pairs_and_linear_match_full_under_schemes(oracle, scheme):
     assert seen["printed"] > 20 and seen["panic"] > 10, seen
 
 
+@pytest.mark.parametrize("scheme", [(5, -4, -8, 1), (5, -4, 2, 1), (5, -4, -20, 3), (2, -3, 0, 1)])
+def test_check_pairs_and_linear_match_full_under_positive_extend(oracle, scheme):
+    """gap_extend > 0: the boundary gains with every column, so unrelated
+    pairs end in a panic node; a pair whose db is its query with a few
+    substitutions keeps the diagonal ahead and prints."""
+    rng = np.random.default_rng(104 + sum(scheme))
+    pairs = []
+    for k in range(100):
+        a = [b"ACGT", b"ACGTN", b"AC"][k % 3]
+        q = rand_seq(rng, int(rng.integers(0, 121)), a)
+        if k % 2:
+            d = bytearray(q)
+            for x in rng.integers(0, max(1, len(d)), len(d) // 16):
+                d[int(x)] = a[int(rng.integers(len(a)))]
+            pairs.append((q, bytes(d)))
+        else:
+            pairs.append((q, rand_seq(rng, int(rng.integers(0, 121)), a)))
+    seen = _batch_vs_single(oracle, pairs, scheme)
+    print(scheme, seen)
+    # (where a gap gains more than it costs, every DFS reaches a boundary first)
+    assert seen["panic"] > 10 and (seen["printed"] > 20 or scheme != (5, -4, -8, 1)), seen
+
+
 def test_check_pairs_and_linear_match_full_past_the_sentinel(oracle):
     rng = np.random.default_rng(103)
     pairs = []
