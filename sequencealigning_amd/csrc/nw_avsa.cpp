@@ -94,10 +94,6 @@ int saln_nw_avsa_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     });
     std::vector<std::vector<uint32_t>> cls(kNumVariants);
     std::vector<uint32_t> fbq;
-    // 8 x 19 groups for queries of <= 152 columns: the per-step overhead over
-    // 19 columns and 7 steps of skew instead of 10 and 15 (C5 slice 6,738 ->
-    // 7,858 GCUPS); option nw.avsa_narrow = 0 keeps the 16 x 10 geometry
-    const bool avsa_narrow = a->opts[Opt::AvsaNarrow] != 0;
     for (uint64_t q = 0; q < n_q; ++q) {
         const uint64_t lq = q_off[q + 1] - q_off[q];
         if (lq > 0x7FFFFFFFull) {
@@ -109,12 +105,7 @@ int saln_nw_avsa_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
             zq.push_back((uint32_t)q);
             continue;
         }
-        int v = choose_variant((uint32_t)lq, a->ld_max, a->sc);
-        // score-only queries of <= 152 columns: 8-lane groups of 19 columns
-        // (variant 4's geometry; no mask, so no walker segment limit)
-        // (32 groups per block stage their db rows in LDS: 4 B per row while
-        // the db stays inside one int16 frame, <= 80 KB per block)
-        if (v == 7 && lq <= 152 && avsa_narrow && a->ld_max <= 600) v = 4;
+        const int v = avsa_variant((uint32_t)lq, a->ld_max, a->sc, a->opts);
         (variant_packed(v) ? cls[v] : fbq).push_back((uint32_t)q);
     }
     a->cells = sum_q * sum_d;
@@ -180,7 +171,7 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
     // or T: checked here on the device, read by the kernel (no host sync)
     const bool prof = a->opts[Opt::AvsaProfile] != 0 && a->n_dn >= 2 &&
                       std::any_of(a->classes.begin(), a->classes.end(),
-                                  [](const saln_nw_avsa::Class &c) { return c.variant == 4; });
+                                  [](const saln_nw_avsa::Class &c) { return c.variant == kNarrowVariant; });
     // the other classes take table penalties under the same check (nw.pk_tab)
     const bool checked = prof || a->opts[Opt::PkTab] != 0;
     const uint32_t *generic = checked ? d_generic : nullptr;
@@ -194,7 +185,7 @@ int saln_nw_avsa_execute(saln_nw_avsa *a, const uint8_t *d_q_seq, const uint8_t 
         // of work-items, so the chunk depends on the class's pairs per block
         const uint64_t kChunk = avsa_chunk_pairs(c.variant);
         uint64_t total = (uint64_t)c.nq * a->n_dn;
-        if (prof && c.variant == 4) {
+        if (prof && c.variant == kNarrowVariant) {
             // whole db pairs through the profile kernel, an odd last db record
             // through the plain one
             const uint64_t tp = (uint64_t)c.nq * (a->n_dn & ~1u);

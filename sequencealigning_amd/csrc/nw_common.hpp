@@ -21,6 +21,7 @@
 // (every maximum real, every cell alive) while the boundary values of its
 // last column and row stay above the sentinel: then V' = 2V + p suffices.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef SALN_HD
@@ -95,21 +96,6 @@ struct SpecStripe {
 struct SpecPair {
     uint32_t plan_idx, n_stripes, stripe_base, reserved;
 };
-struct SpecArgs {
-    const uint2 *blocks;     // spec block -> (spec pair, stripe)
-    const SpecPair *pairs;
-    SpecStripe *stripes;
-    uint32_t *ops;           // kSpecOpsCap words per stripe
-    const uint32_t *done;    // plan index -> walk finished by the spec passes
-    int32_t pass;
-    // column-span walks (nw_span.cpp): span != 0 stops the walk only where
-    // it leaves column span_c0 + 1 (the span's first), not at every stripe edge
-    int32_t span, span_c0;
-    // speculative passes over a span's stripes: stripe entry_s1 - 1 (the
-    // span's rightmost) takes its entry from the record after it on every
-    // pass (0: none)
-    int32_t entry_s1;
-};
 
 // Kernel geometry of one fill variant: G lanes per pair, K query columns per
 // lane, KD = ceil(K/4) mask dwords per lane-row segment (LB = 4*KD bytes).
@@ -157,6 +143,43 @@ struct Geom {
         return (uint64_t)(i - 1) * rs + (uint64_t)(b / G) * cs + (uint64_t)(b % G) * bs + jj0 % K;
     }
 };
+
+// --------- what the fill kernels compute with and the guards (nw_policy.cpp) bound
+// Parent-code format of a fill launch (layouts: nw_kernels.hip, above PlanSrc)
+enum { kCodesWalk = 0, kCodesFull = 1, kCodesNone = 2, kCodesNib = 3 };
+// blocks that fill one pack: 64 consecutive pairs of a variant (pack_block)
+constexpr uint32_t blocks_per_pack(uint32_t pairs_per_block) {
+    return pairs_per_block >= 64 ? 1u : 64u / pairs_per_block;
+}
+// The rebasing packed fill (nw_fill_pk_kernel kRebase; packed_ok_rebase):
+// every kRebaseSteps steps all carried values drop by the column-0 drift of
+// that many rows, (2*gap_extend + alpha) * kRebaseSteps (even: flags
+// survive), so a value at step t is X~ - (2*ge + alpha) * r0(t), r0(t) = t
+// rounded down to the period; a lane's rows are then within period + G of
+// r0 and the values within the bound of a (period + G)-row pair.
+constexpr int kRebaseSteps = 64;
+// The column term of the frame bound is one-sided (a row's values exceed its
+// column-0 value by up to c*(2|m| + 4|ge|) and fall below it by at most a
+// small constant): the frame is centred on half the widest chunk's term.
+SALN_HD int32_t rebase_center(const Scoring &sc, int32_t W) {
+    const int32_t m = sc.match < 0 ? -sc.match : sc.match;
+    const int32_t ge = sc.gap_extend < 0 ? -sc.gap_extend : sc.gap_extend;
+    return (W * (2 * m + 4 * ge) / 2) & ~1;
+}
+// The table fills' extension-free frame (fill_pk_body kFree; pk_free_ok):
+// biased by it, the values are positive normal halves, [0x0400, 0x7BFF].
+constexpr int32_t kFreeBias = 4096;
+// Dynamic LDS cap of the packed fill's staged db rows: two workgroups per CU.
+constexpr size_t kPackedLdsMax = 80 * 1024;
+constexpr size_t kLdsPerCu = 160 * 1024;  // MI355X_MICROARCH.md
+// Bytes of the db rows a block of 256 / G lane groups stages, ld_max the
+// launch's longest db: 4 per row (32-bit row words), 2 in the rebasing xor
+// body, 1 in the i32 fills.  Every guard and every launch takes it from here.
+constexpr size_t staged_lds_bytes(uint32_t G, uint32_t ld_max, uint32_t bytes_per_row) {
+    return (size_t)(256 / G) * (ld_max + 2 * G) * bytes_per_row;
+}
+// Workgroups of a table fill's fallback launch (nw_fill_pk_tabfb_kernel)
+constexpr uint32_t kTabFbBlocks = 64;
 
 // ---------------------------------------------------------------- boundary
 // Reference boundary values (needleman_wunsch_affine.rs:172-216), true scores.

@@ -69,7 +69,9 @@ struct saln_nw_plan {
     uint32_t stripe_sub = kStripeSubMax;  // boundary columns per 256-column chunk
     int stripe_layout() const { return stripe_pk ? 1 : stripe_rows ? 2 : 0; }
     // launch_fill's code format for variant v and whether its launch has a bail word
-    int fill_codes(int v) const { return score_only ? 2 : full_codes ? 1 : nib[v] ? 3 : 0; }
+    int fill_codes(int v) const {
+        return score_only ? kCodesNone : full_codes ? kCodesFull : nib[v] ? kCodesNib : kCodesWalk;
+    }
     bool has_bail() const { return d_bail[async_tb ? buf : 0] != nullptr; }
     bool full_codes = false;  // walk codes (default) or every parent set (decided at creation)
     bool nib[kNumVariants] = {};  // variant stores 4-bit walk codes (Geom::LBn segments)
@@ -363,20 +365,7 @@ int saln::plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     }
     p->cigar_off[n_pairs] = cig;
     clk.mark("plan: descs");
-    {
-        // Queries of 513-1,024 columns: the 64-lane packed variant is the
-        // throughput choice (two pairs per wave), the column stripes the
-        // latency choice (four waves per pair, pipelined): a plan with few
-        // such pairs keeps them on stripes.
-        const uint64_t v8_min = (uint64_t)opts[Opt::WideMinPairs];
-        uint64_t wide = 0;
-        for (const NwPairDesc &d : descs)
-            wide += d.variant == (uint32_t)kWidePackedVariant && d.len_q > 512;
-        if (wide && wide < v8_min)
-            for (NwPairDesc &d : descs)
-                if (d.variant == (uint32_t)kWidePackedVariant && d.len_q > 512)
-                    d.variant = (uint32_t)kStripeVariant;
-    }
+    demote_wide_pairs(descs.data(), descs.size(), opts);
     // plan order: fill pairs grouped by variant, then by query chunk count,
     // longest db first (balances the groups of a block and keeps the pairs of
     // a mask pack alike); pairs with an empty side last (traceback only).
@@ -596,8 +585,9 @@ int saln::plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     if (ooff && (e = dev_alloc(p->ctx, (void **)&p->d_ops, ooff * sizeof(uint32_t))) != hipSuccess)
         return fail(e, "hipMalloc(op stream)");
     // table fills (4-bit codes; full codes in 16-lane groups): a bail word per variant
-    if ((p->var_count[kNarrowVariant] && p->nib[kNarrowVariant]) || (p->var_count[7] && p->nib[7]) ||
-        (p->full_codes && (p->var_count[5] || p->var_count[7]))) {
+    if ((p->var_count[kNarrowVariant] && p->nib[kNarrowVariant]) ||
+        (p->var_count[kPacked16x10] && p->nib[kPacked16x10]) ||
+        (p->full_codes && (p->var_count[kPacked16x16] || p->var_count[kPacked16x10]))) {
         if ((e = dev_alloc(p->ctx, (void **)&p->d_bail[0], kBailBytes)) != hipSuccess ||
             (e = hipMemset(p->d_bail[0], 0, kBailBytes)) != hipSuccess)
             return fail(e, "table fill bail words");
@@ -762,7 +752,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
             if (w1 > w0)
                 HIP_TRY(launch_fill_stripes(p->d_pairs, p->d_work + w0, w1 - w0, d_q, d_db, mask,
                                             p->d_scratch, p->d_prog, p->d_err, endh, p->sc,
-                                            p->score_only ? 2 : p->full_codes ? 1 : 0,
+                                            p->fill_codes(v),
                                             p->stripe_layout(), p->stripe_rows, s, p->opts,
                                             ++p->fill_epoch));
             continue;
@@ -771,8 +761,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
         // one bail word per variant: two table fills queued before either
         // deferred fallback runs must not overwrite each other's epoch
         fx.bail = p->d_bail[cur] ? p->d_bail[cur] + v : nullptr;
-        HIP_TRY(launch_fill(v, p->d_pairs, a, b - a, d_q, d_db, mask, p->d_scratch, endh,
-                            d_results, d_cigar, p->sc,
+        HIP_TRY(launch_fill(v, p->d_pairs, a, b - a, d_q, d_db, mask, p->d_scratch, endh, p->sc,
                             p->fill_codes(v), p->var_maxld[v], s, fx));
     }
     // the fill's end (timed: its timing event doubles as the hand-off)

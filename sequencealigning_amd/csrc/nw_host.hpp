@@ -8,10 +8,27 @@
 
 #include "host_common.hpp"
 #include "nw_common.hpp"
+#include "nw_policy.hpp"
 
 namespace saln {
 
 // kernels (nw_kernels.hip)
+// Arguments of the speculative stripe walks (nw_common.hpp: SpecStripe, SpecPair).
+struct SpecArgs {
+    const uint2 *blocks;     // spec block -> (spec pair, stripe)
+    const SpecPair *pairs;
+    SpecStripe *stripes;
+    uint32_t *ops;           // kSpecOpsCap words per stripe
+    const uint32_t *done;    // plan index -> walk finished by the spec passes
+    int32_t pass;
+    // column-span walks (nw_span.cpp): span != 0 stops the walk only where
+    // it leaves column span_c0 + 1 (the span's first), not at every stripe edge
+    int32_t span, span_c0;
+    // speculative passes over a span's stripes: stripe entry_s1 - 1 (the
+    // span's rightmost) takes its entry from the record after it on every
+    // pass (0: none)
+    int32_t entry_s1;
+};
 // What a packed fill launch needs besides the pairs: the plan's options, the
 // workspace's bail word and the launch's epoch (4-bit-code table fills: the
 // fallback launch runs only when a wave of its table launch left pairs to it).
@@ -25,25 +42,14 @@ struct FillExtras {
     uint32_t epoch = 0;
     std::vector<std::function<hipError_t(hipStream_t)>> *deferred = nullptr;
 };
-// What launch_fill does with a variant's pairs (saln_nw_plan_pair_path reports
-// it): packed int16 halves or i32 lanes; for packed launches the rebasing
-// frame (the longest db leaves the single int16 frame) and the body: 0
-// generic, 2 / 4 the table body at that scale, 3 row profiles.
-struct FillPath {
-    bool packed = false, rebase = false;
-    int table = 0;
-};
-FillPath fill_path(int variant, int codes, uint32_t ld_max, const Scoring &sc, const Options &o,
-                   bool have_bail);
 hipError_t launch_fill(int variant, const NwPairDesc *pairs, uint32_t first, uint32_t count,
                        const uint8_t *qs, const uint8_t *ds, uint8_t *mask, int2 *scratch,
-                       int32_t *end_h, saln_nw_result *results, uint32_t *cigar, Scoring sc,
-                       int codes /* 0 walk, 1 full, 2 none, 3 4-bit walk */, uint32_t ld_max,
+                       int32_t *end_h, Scoring sc, int codes /* kCodes* */, uint32_t ld_max,
                        hipStream_t stream, const FillExtras &fx);
 hipError_t launch_fill_stripes(const NwPairDesc *pairs, const uint2 *work, uint32_t n_work,
                                const uint8_t *qs, const uint8_t *ds, uint8_t *mask,
                                int2 *scratch, uint32_t *prog, uint32_t *err, int32_t *end_h,
-                               Scoring sc, int codes /* 0 walk, 1 full, 2 none */,
+                               Scoring sc, int codes /* kCodesWalk, Full or None */,
                                int layout /* 0 skewed, 1 packed, 2 row-major tiles */,
                                int rows_k /* layout 2: columns per lane */, hipStream_t stream,
                                const Options &o, uint32_t epoch);
@@ -60,32 +66,18 @@ hipError_t launch_next_event(const NwPairDesc *pairs, uint32_t n, const uint8_t 
 hipError_t launch_cigar_compact(const saln_nw_result *res, const uint64_t *src_off,
                                 const uint64_t *dst_off, const uint32_t *src, uint32_t *dst,
                                 uint64_t n, hipStream_t stream);
-constexpr int kStripeVariant = 3;
 // column-stripe pairs: boundary columns allocated per pair (the row fill cuts
 // each 256-column chunk into up to 4 stripes)
 constexpr uint32_t kStripeSubMax = 4;
-// row fill (nw_fill_rows_kernel) columns per lane, 0 = the skewed stripe fill;
-// waves_k1: the plan's stripe waves at one column per lane
-int stripe_rows_k(uint64_t waves_k1, const Options &o);
-// column stripes run the packed (int16 halves) fill for this scoring and
-// this many stripe waves in the plan (decided once per plan: it sets the layout)
-bool stripe_packed(const Scoring &sc, uint64_t n_waves, bool wide, const Options &o);
-constexpr int kWidePackedVariant = 8;        // packed, 64-lane groups, up to 1,024 columns
-constexpr uint64_t kWidePackedMinPairs = 1536;  // fewer such pairs: column stripes (measured crossover 1,024-2,048)
 hipError_t launch_score_results(const NwPairDesc *pairs, uint32_t first, uint32_t n,
                                 const int32_t *end_h, saln_nw_result *results, Scoring sc,
                                 hipStream_t stream);
 hipError_t launch_traceback(int variant, const NwPairDesc *pairs, uint32_t first, uint32_t n,
-                            const uint8_t *qs,
-                            const uint8_t *ds, const uint8_t *mask, const int32_t *end_h,
-                            uint32_t *ops, saln_nw_result *results, uint32_t *cigar, Scoring sc,
-                            int stripe_layout, hipStream_t stream,
+                            const uint8_t *qs, const uint8_t *ds, const uint8_t *mask,
+                            const int32_t *end_h, uint32_t *ops, saln_nw_result *results,
+                            uint32_t *cigar, Scoring sc, int stripe_layout, hipStream_t stream,
                             const uint32_t *spec_done = nullptr, bool nib = false,
                             uint32_t walk_waves = 0);
-// variants whose walk codes may be 4-bit (kCodesNib): the short-query packed
-// fills 7 (16 x 10) and 4 (8 x 19, 4-bit only)
-inline bool variant_nib(int v) { return v == 7 || v == 4; }
-constexpr int kNarrowVariant = 4;  // 8 x 19 groups, queries of <= 152 columns
 // speculative stripe walks of the plan's long column-stripe pairs: `passes`
 // walk passes, the link (accept or leave to the cooperative walker, `done`)
 // and the CIGAR copy; strict_err (SALN_SPEC_STRICT=1, tests): bit 1 set when a
@@ -110,10 +102,7 @@ hipError_t launch_span_spec(const NwPairDesc *pairs, SpecArgs sa, uint32_t n_blo
                             const uint8_t *qs, const uint8_t *ds, const uint8_t *mask,
                             const int32_t *end_h, Scoring sc, hipStream_t stream,
                             int pass_lo = 1);
-// score-only all-vs-all (nw_avsa.cpp); avsa_chunk_pairs: the most pairs one
-// launch of a packed class may take (0: not a packed variant)
-uint64_t avsa_chunk_pairs(int variant);
-uint64_t avsa_launch_blocks(int variant, uint64_t count);  // workgroups of one launch
+// score-only all-vs-all (nw_avsa.cpp)
 hipError_t launch_avsa_prof(const uint64_t *q_off, const uint64_t *d_off, const uint32_t *q_ids,
                             uint32_t nq, const uint32_t *d_ids, uint32_t nq_total, uint64_t base,
                             uint32_t count, const uint8_t *qs, const uint8_t *ds, int2 *out,
@@ -132,9 +121,6 @@ hipError_t launch_avsa_boundary(const uint64_t *q_off, const uint64_t *d_off,
 hipError_t launch_avsa_scatter(const saln_nw_result *res, const uint32_t *q_ids, uint32_t nq,
                                const uint32_t *d_ids, uint64_t n, uint32_t nq_total, int2 *out,
                                hipStream_t stream);
-Geom variant_geom(int v);
-bool variant_packed(int v);
-int choose_variant(uint32_t len_q, uint32_t len_db, const Scoring &sc, bool narrow = false);
 
 Scoring scoring_or_default(const saln_nw_scoring *s);
 

@@ -19,8 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -28,10 +26,6 @@
 #include "nw_host.hpp"
 #include "saln_options.hpp"
 #include "saln.h"
-
-namespace saln {
-bool stripe_packed(const Scoring &sc, uint64_t n_waves, bool wide, const Options &o);
-}
 
 namespace saln {
 
@@ -54,9 +48,6 @@ __device__ __forceinline__ uint32_t pack_block(uint32_t bpp, uint32_t i = blockI
     const uint32_t sup = 8u * bpp;
     const uint32_t r = i % sup;
     return i - r + (r % 8u) * bpp + r / 8u;
-}
-constexpr uint32_t blocks_per_pack(uint32_t pairs_per_block) {
-    return pairs_per_block >= 64 ? 1u : 64u / pairs_per_block;
 }
 
 // --------------------------------------------------------------- traceback
@@ -872,7 +863,7 @@ constexpr int32_t kCoopSlack = 64;  // rows loaded beyond a diagonal crossing of
 // packed stripe layout (bs == 0): virtual lane v = (c - c0) / 2 of row r sits
 // on line r - 1 + v (127 lines of skew); 2 the row-major 256-column tiles of
 // nw_fill_rows_kernel (no skew: row r is line r - 1).
-// kSpec: one block per walker stripe of a long pair (SpecArgs, nw_common.hpp):
+// kSpec: one block per walker stripe of a long pair (SpecArgs, nw_host.hpp):
 // the walk starts at the stripe's entry and stops where it leaves the stripe
 // (the crossing step is the stripe's last op) or ends; it writes its run
 // words and exit to the stripe's record.  A pass whose entry equals the one
@@ -1504,8 +1495,6 @@ struct NibSeg {
 // segment (Geom::LBn): the 4-column groups g = c / 4 as 16-bit halves, two
 // per dword, in each half the nibble of column c at bit 8 (c & 1) +
 // 4 ((c >> 1) & 1); then the db char at byte Geom::nib_char_byte.
-enum { kCodesWalk = 0, kCodesFull = 1, kCodesNone = 2, kCodesNib = 3 };
-
 // Where the packed fill gets its pairs and puts the end values.
 // PlanSrc: the plan's sorted descriptor table; the scaled end value goes to
 // end_h for the traceback / score-results kernels.
@@ -1571,23 +1560,9 @@ struct AvsaSrcP : AvsaSrc {
 // lane group (G*K = the same width, fewer lanes: less pipeline skew, per-step
 // overhead spread over more columns) write the layout of the wider one.
 //
-// kRebase: pairs whose db is too long for one int16 frame (packed_ok_rebase).
-// Every kRebaseSteps steps all carried values drop by the column-0 drift of
-// that many rows, (2*gap_extend + alpha) * kRebaseSteps (even: flags
-// survive), so a value at step t is X~ - (2*ge + alpha) * r0(t), r0(t) = t
-// rounded down to the period; a lane's rows are then within period + G of
-// r0 and the values within the bound of a (period + G)-row pair.  Parent
-// codes compare values of one cell (frame-free); group-start inputs and end
-// values convert with r0(t).
-constexpr int kRebaseSteps = 64;
-// The column term of the frame bound is one-sided (a row's values exceed its
-// column-0 value by up to c*(2|m| + 4|ge|) and fall below it by at most a
-// small constant): the frame is centred on half the widest chunk's term.
-__host__ __device__ inline int32_t rebase_center(const Scoring &sc, int32_t W) {
-    const int32_t m = sc.match < 0 ? -sc.match : sc.match;
-    const int32_t ge = sc.gap_extend < 0 ? -sc.gap_extend : sc.gap_extend;
-    return (W * (2 * m + 4 * ge) / 2) & ~1;
-}
+// kRebase: pairs whose db is too long for one int16 frame (packed_ok_rebase;
+// kRebaseSteps, rebase_center: nw_common.hpp).  Parent codes compare values of
+// one cell (frame-free); group-start inputs and end values convert with r0(t).
 
 // (Built for one wave per SIMD: at 124 VGPRs it runs 4; built for 5, 96
 // VGPRs, it spills 26 registers: C2 fill 0.97 -> 1.57 ms, round 1.)
@@ -1616,7 +1591,6 @@ constexpr int pk_min_waves() { return kCodes == 3 /* kCodesNib */ && G == 8 ? 3 
 // stays within the packed bound: X~ = X' + 2|ge|(r + c) lies in
 // [-(4|go| + ...), rows (2|m| + 2|ge|) + 2|ge| lq] (X' is at least its
 // all-gap path, at most its all-match one).
-constexpr int32_t kFreeBias = 4096;
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // max of three words of two biased halves read as positive normal f16 (one
 // v_pk_maximum3_f16); exact only inside the extension-free frame's window
@@ -2168,12 +2142,11 @@ __global__ __launch_bounds__(256, (pk_min_waves<G, K, kCodes>())) void nw_fill_p
 }
 // (kRebaseGeneric: the fallback of a launch whose dbs need the rebasing frame;
 // the extension-free table body has no drift and needs none)
-// A grid-stride launch over the table launch's `vblocks` blocks (64
+// A grid-stride launch over the table launch's `vblocks` blocks (kTabFbBlocks
 // workgroups instead of one per block: the launch behind every table fill
 // mostly finds its word unset, and its workgroups' dispatch was its time - a
 // full grid of waves that only read the word took 42 us per C2 step, 512
 // workgroups 27 us; round 6).
-constexpr uint32_t kTabFbBlocks = 64;
 template <int G, int K, typename Src, bool kRebaseGeneric, int kCodes = kCodesNib>
 __global__ __launch_bounds__(256, (pk_min_waves<G, K, kCodes>())) void nw_fill_pk_tabfb_kernel(
     Src src, uint32_t count, const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds,
@@ -3224,277 +3197,144 @@ hipError_t launch_score_results(const NwPairDesc *pairs, uint32_t first, uint32_
     return hipGetLastError();
 }
 
-// ----------------------------------------------------------------- launchers
-// variants 0-3: i32 lanes; 4-6: packed i16 (two pairs per lane)
-constexpr Geom kVariants[kNumVariants] = {{16, 10}, {16, 16}, {64, 8}, {64, 4},
-                                          {8, 19},  {16, 16}, {32, 16}, {16, 10}, {64, 16}};
-constexpr bool kPacked[kNumVariants] = {false, false, false, false, true, true, true, true, true};
-// Lanes per pair of each variant's fill kernel.  (8-lane groups of 20
-// columns writing variant 7's layout measured equal in round 1: 202 VGPRs
-// halve the occupancy.)
-constexpr uint32_t kFillG[kNumVariants] = {16, 16, 64, 64, 8, 16, 32, 16, 64};
+// ------------------ launchers (every decision they take: nw_policy.cpp)
+template <int N>
+using IntC = std::integral_constant<int, N>;
 
+// Calls f(G, K, v) with variant v's lane-group geometry (kVariantTable) and
+// its id as integral constants; a variant out of range: hipErrorInvalidValue.
+template <int V = 0, typename F>
+static hipError_t dispatch_variant(int v, F &&f) {
+    if constexpr (V == kNumVariants) return hipErrorInvalidValue;
+    else if (v != V) return dispatch_variant<V + 1>(v, f);
+    else return f(IntC<(int)kVariantTable[V].g.G>{}, IntC<(int)kVariantTable[V].g.K>{}, IntC<V>{});
+}
 
-// Dynamic LDS cap of the packed fill's staged db rows: two workgroups per CU.
-constexpr size_t kPackedLdsMax = 80 * 1024;
-constexpr size_t kLdsPerCu = 160 * 1024;  // MI355X_MICROARCH.md
-static bool packed_ok(uint32_t lq, uint32_t ld, const Scoring &sc);
-static bool packed_single_ok(uint32_t G, uint32_t W, uint32_t ld, const Scoring &sc);
+// Calls f with the code format as an integral constant; 4-bit walk codes
+// only where the launch has kernels for them (kNib: the packed fills).
+template <bool kNib = false, typename F>
+static hipError_t dispatch_codes(int codes, F &&f) {
+    if (codes == kCodesWalk) return f(IntC<kCodesWalk>{});
+    if (codes == kCodesFull) return f(IntC<kCodesFull>{});
+    if (codes == kCodesNone) return f(IntC<kCodesNone>{});
+    if constexpr (kNib)
+        if (codes == kCodesNib) return f(IntC<kCodesNib>{});
+    return hipErrorInvalidValue;
+}
+
+// Raises a kernel's dynamic LDS limit where its launch stages more than 64 KB of db rows.
+static hipError_t allow_lds(const void *kern, size_t lds) {
+    if (lds <= 65536) return hipSuccess;
+    return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPackedLdsMax);
+}
+
+// Calls f with std::true_type or std::false_type for b.
+template <typename F>
+static hipError_t dispatch_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 template <int G, int K>
-static void fill_i32(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uint32_t first,
-                     uint32_t count, const uint8_t *qs, const uint8_t *ds, uint8_t *mask,
-                     int2 *scratch, int32_t *end_h, saln_nw_result *, uint32_t *, Scoring sc,
-                     int codes, uint32_t ld_max) {
-    const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G);
+static hipError_t fill_i32(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uint32_t first,
+                           uint32_t count, const uint8_t *qs, const uint8_t *ds, uint8_t *mask,
+                           int2 *scratch, int32_t *end_h, Scoring sc, int codes, uint32_t ld_max) {
+    const size_t lds = staged_lds_bytes(G, ld_max, 1);
     const int32_t pen_max = 4 * (sc.match - sc.mismatch);  // the i32 fills' V'' scale
-    auto go = [&](auto codes_c, auto minpen_c, auto staged_c) {
-        nw_fill_lanes_kernel<G, K, decltype(codes_c)::value, decltype(minpen_c)::value,
-                             decltype(staged_c)::value>
-            <<<grid, dim3(256), decltype(staged_c)::value ? lds : 0, s>>>(
-                pairs, first, count, qs, ds, mask, scratch, end_h, sc, ld_max);
-    };
-    auto by_staged = [&](auto codes_c, auto minpen_c) {
-        if (lds <= 65536) go(codes_c, minpen_c, std::true_type{});
-        else go(codes_c, minpen_c, std::false_type{});
-    };
-    auto by_pen = [&](auto codes_c) {
-        if (pen_max >= 0 && pen_max <= 256) by_staged(codes_c, std::true_type{});
-        else by_staged(codes_c, std::false_type{});
-    };
-    if (codes == kCodesFull) by_pen(std::integral_constant<int, kCodesFull>{});
-    else if (codes == kCodesNone) by_pen(std::integral_constant<int, kCodesNone>{});
-    else by_pen(std::integral_constant<int, kCodesWalk>{});
-}
-
-// The table-penalty fill's bonuses fit a byte (fill_pk_body, kTab) and its
-// frame's floor, a few opens below zero, stays far inside int16.
-static bool pk_tab_ok(const Scoring &sc) {
-    const int64_t cm = 2ll * sc.match - 4ll * sc.gap_extend, cmm = 2ll * sc.mismatch - 4ll * sc.gap_extend;
-    return cmm >= 0 && cm <= 255 && cmm < cm && -(int64_t)sc.gap_open <= 2000;
-}
-// ... and its values, biased by kFreeBias, stay positive normal halves for
-// W-column lanes groups over `rows` rows: X~ = X' + 2|ge|(r + c) is at least
-// the all-gap path's 4go + 4ge less an open and a mismatch for M / I / D, at
-// most rows (2|m| + 2|ge|) + 2|ge| W plus the boundary flag.
-// scale: 2 (V = 2x + p) or 4 (the scale-4 table body, kTabMode 4): every
-// bound scales with it, and its bonuses must still fit a byte.
-static bool pk_free_ok(const Scoring &sc, uint32_t W, uint32_t rows, int scale = 2) {
-    if (!pk_tab_ok(sc)) return false;
-    const int64_t m = std::abs(sc.match), mm = std::abs(sc.mismatch), ge = std::abs(sc.gap_extend),
-                  go = std::abs(sc.gap_open);
-    const int64_t f = scale / 2;
-    if (f * (2ll * sc.match - 4ll * sc.gap_extend) > 255) return false;
-    const int64_t lo = f * (6 * go + 6 * ge + 2 * mm + 64);
-    const int64_t hi = f * ((int64_t)rows * (2 * m + 2 * ge) + 2 * ge * (int64_t)W + 2 * go + 64);
-    return lo <= kFreeBias - 0x400 && hi <= 0x7BFF - kFreeBias;
-}
-
-// The body a packed plan launch of G x K lane groups runs (FillPath::table):
-// the table body where the launch stores 4-bit walk codes, or full parent
-// sets in 16-lane groups, nw.pk_tab is on, the workspace has a bail word, the
-// extension-free frame holds `ld_max` rows (pk_free_ok) and the 32-bit staged
-// rows fit the LDS; else the generic body.  nw.pk_tab 1: scale 2; 2: the
-// scale-4 body where its window holds the launch, else scale 2; 3: row
-// profiles (scale 2).  Full parent sets: row profiles.
-static int pk_table_body(uint32_t G, uint32_t K, int codes, uint32_t ld_max, bool rebase,
-                         const Scoring &sc, const Options &o, bool have_bail) {
-    if (codes != kCodesNib && !(codes == kCodesFull && G == 16)) return 0;
-    // (the table body stages 32-bit row words; a rebasing fallback 16-bit ones)
-    // (and keeps four workgroups per CU where the rebasing fill had them)
-    const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G) * (rebase ? 2 : 4);
-    const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
-    if (!o[Opt::PkTab] || !have_bail || !pk_free_ok(sc, G * K, ld_max) ||
-        lds_tab > std::max(lds, kLdsPerCu / 4))
-        return 0;
-    if (codes == kCodesFull) return 3;
-    return o[Opt::PkTab] == 2 && pk_free_ok(sc, G * K, ld_max, 4) ? 4 : o[Opt::PkTab] == 3 ? 3 : 2;
-}
-
-FillPath fill_path(int variant, int codes, uint32_t ld_max, const Scoring &sc, const Options &o,
-                   bool have_bail) {
-    FillPath fp;
-    fp.packed = kPacked[variant];
-    if (!fp.packed) return fp;
-    // packed pairs beyond one int16 frame (packed_ok_rebase) take the rebasing fill
-    fp.rebase = !packed_single_ok(kVariants[variant].G, kVariants[variant].W(), ld_max, sc);
-    fp.table = pk_table_body(kVariants[variant].G, kVariants[variant].K, codes, ld_max, fp.rebase,
-                             sc, o, have_bail);
-    return fp;
+    return dispatch_codes(codes, [&](auto codes_c) {
+        return dispatch_bool(pen_max >= 0 && pen_max <= 256, [&](auto minpen_c) {
+            return dispatch_bool(lds <= 65536, [&](auto staged_c) {
+                constexpr bool kStaged = decltype(staged_c)::value;
+                nw_fill_lanes_kernel<G, K, decltype(codes_c)::value, decltype(minpen_c)::value, kStaged>
+                    <<<grid, dim3(256), kStaged ? lds : 0, s>>>(pairs, first, count, qs, ds, mask,
+                                                                scratch, end_h, sc, ld_max);
+                return hipSuccess;
+            });
+        });
+    });
 }
 
 template <int G, int K, int KS = K>
 static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uint32_t first,
                           uint32_t count, const uint8_t *qs, const uint8_t *ds, uint8_t *mask,
-                          int32_t *end_h, saln_nw_result *, uint32_t *, Scoring sc,
-                          int codes, uint32_t ld_max, const FillPath &fp, const FillExtras &fx) {
-    const bool rebase = fp.rebase;
-    const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G) * (rebase ? 2 : 4);
+                          int32_t *end_h, Scoring sc, int codes, uint32_t ld_max,
+                          const FillPath &fp, const FillExtras &fx) {
+    const size_t lds = staged_lds_bytes(G, ld_max, fp.rebase ? 2 : 4);
     if (lds > kPackedLdsMax) return hipErrorInvalidValue;  // choose_variant keeps ld below this
     const PlanSrc src{pairs, first, end_h};
-    auto big_lds = [](std::initializer_list<const void *> fs, size_t n) -> hipError_t {
-        if (n <= 65536) return hipSuccess;
-        for (const void *f : fs) {
-            const hipError_t e =
-                hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPackedLdsMax);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    };
     auto go = [&](auto codes_c, auto rebase_c) -> hipError_t {
-        const auto kern = nw_fill_pk_kernel<G, K, decltype(codes_c)::value, PlanSrc, KS,
-                                            decltype(rebase_c)::value>;
-        if constexpr (decltype(codes_c)::value == kCodesNib && KS == K) {
-            const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
+        constexpr int kC = decltype(codes_c)::value;
+        constexpr bool kRb = decltype(rebase_c)::value;
+        // the table body (fill_path, pk_table_body): 4-bit walk codes, or full
+        // parent sets (round 6) with row profiles for the 16-lane geometries
+        // (queries of up to 256 columns)
+        if constexpr (KS == K && (kC == kCodesNib || (kC == kCodesFull && G == 16))) {
             if (fp.table) {
-                constexpr bool kRb = decltype(rebase_c)::value;
-                const size_t lds_prof = lds_tab;
-                const int sel = fp.table;  // pk_table_body
-                const void *tk = sel == 4 ? (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 4>
-                                 : sel == 3 ? (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 3>
-                                            : (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 2>;
-                const size_t lds_k = sel == 3 ? lds_prof : lds_tab;
-                hipError_t e = big_lds({tk}, lds_k);
-                if (e == hipSuccess)
-                    e = big_lds({(const void *)nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb>}, lds_tab);
-                if (e != hipSuccess) return e;
-                if (sel == 4)
-                    nw_fill_pk_tab_kernel<G, K, PlanSrc, 4><<<grid, dim3(256), lds_k, s>>>(
-                        src, count, qs, ds, mask, sc, ld_max, fx.bail, fx.epoch);
-                else if (sel == 3)
-                    nw_fill_pk_tab_kernel<G, K, PlanSrc, 3><<<grid, dim3(256), lds_k, s>>>(
-                        src, count, qs, ds, mask, sc, ld_max, fx.bail, fx.epoch);
-                else
-                    nw_fill_pk_tab_kernel<G, K, PlanSrc, 2><<<grid, dim3(256), lds_k, s>>>(
-                        src, count, qs, ds, mask, sc, ld_max, fx.bail, fx.epoch);
-                auto fb = [=, bail = fx.bail, epoch = fx.epoch](hipStream_t fs) {
-                    nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb>
-                        <<<dim3(std::min(grid.x, kTabFbBlocks)), dim3(256), lds_tab, fs>>>(
+                const size_t lds_tab = staged_lds_bytes(G, ld_max, 4);
+                auto table = [&](auto scale_c) -> hipError_t {
+                    const auto tk = nw_fill_pk_tab_kernel<G, K, PlanSrc, decltype(scale_c)::value, kC>;
+                    const auto fk = nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb, kC>;
+                    hipError_t e = allow_lds((const void *)tk, lds_tab);
+                    if (e == hipSuccess) e = allow_lds((const void *)fk, lds_tab);
+                    if (e != hipSuccess) return e;
+                    tk<<<grid, dim3(256), lds_tab, s>>>(src, count, qs, ds, mask, sc, ld_max,
+                                                        fx.bail, fx.epoch);
+                    auto fb = [=, bail = fx.bail, epoch = fx.epoch](hipStream_t fs) {
+                        fk<<<dim3(std::min(grid.x, kTabFbBlocks)), dim3(256), lds_tab, fs>>>(
                             src, count, qs, ds, mask, sc, ld_max, bail, epoch, grid.x);
-                    return hipGetLastError();
+                        return hipGetLastError();
+                    };
+                    if (fx.deferred) fx.deferred->push_back(fb);
+                    else return fb(s);
+                    return hipSuccess;
                 };
-                if (fx.deferred) fx.deferred->push_back(fb);
-                else return fb(s);
-                return hipSuccess;
+                if constexpr (kC == kCodesFull) return table(IntC<3>{});
+                else if (fp.table == 4) return table(IntC<4>{});
+                else return fp.table == 3 ? table(IntC<3>{}) : table(IntC<2>{});
             }
         }
-        // full parent sets (round 6): the table body with row profiles for the
-        // 16-lane geometries (queries of up to 256 columns), nw.pk_tab != 0
-        if constexpr (decltype(codes_c)::value == kCodesFull && KS == K && G == 16) {
-            const size_t lds_tab = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
-            if (fp.table) {
-                constexpr bool kRb = decltype(rebase_c)::value;
-                const void *tk = (const void *)nw_fill_pk_tab_kernel<G, K, PlanSrc, 3, kCodesFull>;
-                const void *fk = (const void *)nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb, kCodesFull>;
-                hipError_t e = big_lds({tk, fk}, lds_tab);
-                if (e != hipSuccess) return e;
-                nw_fill_pk_tab_kernel<G, K, PlanSrc, 3, kCodesFull><<<grid, dim3(256), lds_tab, s>>>(
-                    src, count, qs, ds, mask, sc, ld_max, fx.bail, fx.epoch);
-                auto fb = [=, bail = fx.bail, epoch = fx.epoch](hipStream_t fs) {
-                    nw_fill_pk_tabfb_kernel<G, K, PlanSrc, kRb, kCodesFull>
-                        <<<dim3(std::min(grid.x, kTabFbBlocks)), dim3(256), lds_tab, fs>>>(
-                            src, count, qs, ds, mask, sc, ld_max, bail, epoch, grid.x);
-                    return hipGetLastError();
-                };
-                if (fx.deferred) fx.deferred->push_back(fb);
-                else return fb(s);
-                return hipSuccess;
-            }
-        }
-        const hipError_t e = big_lds({(const void *)kern}, lds);
+        const auto kern = nw_fill_pk_kernel<G, K, kC, PlanSrc, KS, kRb>;
+        const hipError_t e = allow_lds((const void *)kern, lds);
         if (e != hipSuccess) return e;
         kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, mask, sc, ld_max, true);
         return hipSuccess;
     };
-    auto by_codes = [&](auto rebase_c) {
-        if (codes == kCodesFull) return go(std::integral_constant<int, kCodesFull>{}, rebase_c);
-        if (codes == kCodesNone) return go(std::integral_constant<int, kCodesNone>{}, rebase_c);
-        // the short-query variants (7: 16 x 10, 4: 8 x 19) store 4-bit walk
-        // codes, the wider ones bytes
-        if constexpr (G * K <= 160) {
-            if (codes == kCodesNib) return go(std::integral_constant<int, kCodesNib>{}, rebase_c);
-            return hipErrorInvalidValue;
-        } else {
-            if (codes == kCodesWalk) return go(std::integral_constant<int, kCodesWalk>{}, rebase_c);
-            return hipErrorInvalidValue;
-        }
-    };
-    return rebase ? by_codes(std::true_type{}) : by_codes(std::false_type{});
-}
-
-// Blocks of a score-only all-vs-all launch of `count` pairs with G-lane
-// groups: two pairs per group, 256 / G groups per block, rounded up to whole
-// XCD super-blocks of 8 * blocks_per_pack blocks (pack_block).
-static uint64_t avsa_blocks(uint32_t G, uint64_t count) {
-    const uint64_t gpb = 256 / G, sup = 8 * blocks_per_pack(2 * (uint32_t)gpb);
-    const uint64_t groups = (count + 1) / 2;
-    return ((groups + gpb - 1) / gpb + sup - 1) / sup * sup;
-}
-
-static uint32_t avsa_lanes(int variant) {
-    switch (variant) {
-        case 4: return 8;
-        case 5: case 7: return 16;
-        case 6: return 32;
-        case 8: return 64;
-        default: return 0;
-    }
-}
-
-// The most pairs one launch of a packed class may take: the dispatch packet's
-// grid size is a 32-bit count of work-items (blocks * 256 <= 2^32 - 1), so
-// the largest whole number of super-blocks below that, two pairs per group.
-uint64_t avsa_chunk_pairs(int variant) {
-    const uint32_t G = avsa_lanes(variant);
-    if (!G) return 0;
-    const uint64_t gpb = 256 / G, sup = 8 * blocks_per_pack(2 * (uint32_t)gpb);
-    const uint64_t blocks = (0xFFFFFFFFull / 256) / sup * sup;
-    return std::min<uint64_t>(blocks * gpb * 2, 0x80000000ull);  // count is a uint32
-}
-
-uint64_t avsa_launch_blocks(int variant, uint64_t count) {
-    const uint32_t G = avsa_lanes(variant);
-    return G ? avsa_blocks(G, count) : 0;
+    return dispatch_bool(fp.rebase, [&](auto rebase_c) {
+        return dispatch_codes<true>(codes, [&](auto codes_c) -> hipError_t {
+            // the short-query variants (16 x 10, 8 x 19) store 4-bit walk
+            // codes, the wider ones bytes
+            if constexpr (decltype(codes_c)::value == (G * K <= 160 ? kCodesWalk : kCodesNib))
+                return hipErrorInvalidValue;
+            else return go(codes_c, rebase_c);
+        });
+    });
 }
 
 template <int G, int K>
 static hipError_t avsa_pk(const AvsaSrc &src, uint32_t count, const uint8_t *qs, const uint8_t *ds,
                           Scoring sc, uint32_t ld_max, hipStream_t s, const uint32_t *generic,
                           const Options &o) {
-    constexpr uint32_t gpb = 256 / G;
-    const uint64_t blocks = avsa_blocks(G, count);
+    const uint64_t blocks = packed_blocks(G, count);
     if (blocks * 256 > 0xFFFFFFFFull) return hipErrorInvalidConfiguration;  // 32-bit grid
     const dim3 grid((uint32_t)blocks);
     const bool rebase = !packed_single_ok(G, G * K, ld_max, sc);
-    const size_t lds = (size_t)gpb * (ld_max + 2 * G) * (rebase ? 2 : 4);
+    const size_t lds = staged_lds_bytes(G, ld_max, rebase ? 2 : 4);
     if (lds > kPackedLdsMax) return hipErrorInvalidValue;
-    // the table body stages 32-bit row words, the rebasing xor body 16-bit ones
-    const size_t lds_tab = (size_t)gpb * (ld_max + 2 * G) * 4;
-    const bool tab = generic && o[Opt::PkTab] && pk_free_ok(sc, G * K, ld_max) &&
-                     lds_tab <= std::max(lds, kLdsPerCu / 4);
-    auto go = [&](auto rebase_c) -> hipError_t {
+    const size_t lds_tab = staged_lds_bytes(G, ld_max, 4);  // the table body: 32-bit row words
+    const bool tab = generic && pk_table_ok(G, K, ld_max, rebase, sc, o);
+    return dispatch_bool(rebase, [&](auto rebase_c) -> hipError_t {
         if (tab) {
             const auto kern = nw_fill_avsa_tab_kernel<G, K, decltype(rebase_c)::value>;
-            if (lds_tab > 65536) {
-                const hipError_t e = hipFuncSetAttribute(
-                    (const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                    (int)kPackedLdsMax);
-                if (e != hipSuccess) return e;
-            }
+            const hipError_t e = allow_lds((const void *)kern, lds_tab);
+            if (e != hipSuccess) return e;
             kern<<<grid, dim3(256), lds_tab, s>>>(src, count, qs, ds, sc, ld_max, true, generic);
             return hipSuccess;
         }
         const auto kern = nw_fill_pk_kernel<G, K, kCodesNone, AvsaSrc, K, decltype(rebase_c)::value>;
-        if (lds > 65536) {
-            const hipError_t e = hipFuncSetAttribute((const void *)kern,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)kPackedLdsMax);
-            if (e != hipSuccess) return e;
-        }
+        const hipError_t e = allow_lds((const void *)kern, lds);
+        if (e != hipSuccess) return e;
         kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, nullptr, sc, ld_max, true);
         return hipSuccess;
-    };
-    return rebase ? go(std::true_type{}) : go(std::false_type{});
+    });
 }
 
 // The 8 x 19 class with query profiles (AvsaSrcP: count even, pairs
@@ -3506,23 +3346,19 @@ hipError_t launch_avsa_prof(const uint64_t *q_off, const uint64_t *d_off, const 
                             uint32_t count, const uint8_t *qs, const uint8_t *ds, int2 *out,
                             Scoring sc, uint32_t ld_max, const uint32_t *generic,
                             hipStream_t stream, const Options &o) {
-    constexpr int G = 8, K = 19;
+    constexpr int G = kVariantTable[kNarrowVariant].g.G, K = kVariantTable[kNarrowVariant].g.K;
     if (!count) return hipSuccess;
-    if ((count | base) & 1u || !packed_ok(G * K, ld_max, sc)) return hipErrorInvalidValue;
+    if ((count | base) & 1u || !packed_range_ok(G * K, ld_max, sc)) return hipErrorInvalidValue;
     AvsaSrcP src;
     static_cast<AvsaSrc &>(src) = AvsaSrc{q_off, d_off, q_ids, d_ids, nq, nq_total, base, out};
-    const uint64_t blocks = avsa_blocks(G, count);
+    const uint64_t blocks = packed_blocks(G, count);
     if (blocks * 256 > 0xFFFFFFFFull) return hipErrorInvalidConfiguration;
-    const size_t lds = (size_t)(256 / G) * (ld_max + 2 * G) * 4;
+    const size_t lds = staged_lds_bytes(G, ld_max, 4);
     if (lds > kPackedLdsMax) return hipErrorInvalidValue;
-    const auto kern = o[Opt::PkTab] && pk_free_ok(sc, G * K, ld_max) ? nw_fill_avsa_prof_kernel<G, K, true>
-                                                       : nw_fill_avsa_prof_kernel<G, K, false>;
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute((const void *)kern,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)kPackedLdsMax);
-        if (e != hipSuccess) return e;
-    }
+    const auto kern = pk_table_ok(G, K, ld_max, false, sc, o) ? nw_fill_avsa_prof_kernel<G, K, true>
+                                                              : nw_fill_avsa_prof_kernel<G, K, false>;
+    const hipError_t e = allow_lds((const void *)kern, lds);
+    if (e != hipSuccess) return e;
     kern<<<dim3((uint32_t)blocks), dim3(256), lds, stream>>>(src, count, qs, ds, sc, ld_max,
                                                               true, generic);
     return hipGetLastError();
@@ -3535,7 +3371,7 @@ hipError_t launch_acgt_check(const uint8_t *seq, uint64_t n, uint32_t *flag, hip
     return hipGetLastError();
 }
 
-// Score-only all-vs-all over one packed query class (variant 4-7): pairs
+// Score-only all-vs-all over one packed query class: pairs
 // [base, base + count) of the class's (query, db) index space.
 hipError_t launch_avsa(int variant, const uint64_t *q_off, const uint64_t *d_off,
                        const uint32_t *q_ids, uint32_t nq, const uint32_t *d_ids,
@@ -3544,17 +3380,14 @@ hipError_t launch_avsa(int variant, const uint64_t *q_off, const uint64_t *d_off
                        hipStream_t stream, const Options &o, const uint32_t *generic) {
     if (!count) return hipSuccess;
     const AvsaSrc src{q_off, d_off, q_ids, d_ids, nq, nq_total, base, out};
-    hipError_t e;
-    switch (variant) {
-        case 4: e = avsa_pk<8, 19>(src, count, qs, ds, sc, ld_max, stream, generic, o); break;
-        case 5: e = avsa_pk<16, 16>(src, count, qs, ds, sc, ld_max, stream, generic, o); break;
-        case 6: e = avsa_pk<32, 16>(src, count, qs, ds, sc, ld_max, stream, generic, o); break;
-        case 7: e = avsa_pk<16, 10>(src, count, qs, ds, sc, ld_max, stream, generic, o); break;
-        case 8: e = avsa_pk<64, 16>(src, count, qs, ds, sc, ld_max, stream, generic, o); break;
-        default: return hipErrorInvalidValue;
-    }
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    return dispatch_variant(variant, [&](auto g_c, auto k_c, auto v_c) -> hipError_t {
+        if constexpr (!kVariantTable[decltype(v_c)::value].packed) return hipErrorInvalidValue;
+        else {
+            const hipError_t e = avsa_pk<decltype(g_c)::value, decltype(k_c)::value>(
+                src, count, qs, ds, sc, ld_max, stream, generic, o);
+            return e != hipSuccess ? e : hipGetLastError();
+        }
+    });
 }
 
 // Pairs with an empty side (no fill): out[d * nq_total + q] from the
@@ -3604,39 +3437,44 @@ hipError_t launch_avsa_scatter(const saln_nw_result *res, const uint32_t *q_ids,
 
 hipError_t launch_fill(int variant, const NwPairDesc *pairs, uint32_t first, uint32_t count,
                        const uint8_t *qs, const uint8_t *ds, uint8_t *mask, int2 *scratch,
-                       int32_t *end_h, saln_nw_result *res, uint32_t *cig, Scoring sc,
-                       int codes, uint32_t ld_max, hipStream_t stream, const FillExtras &fx) {
+                       int32_t *end_h, Scoring sc, int codes, uint32_t ld_max, hipStream_t stream,
+                       const FillExtras &fx) {
     if (count == 0) return hipSuccess;
-    const uint32_t gpb = 256 / kFillG[variant];  // lane groups per block
-    const uint32_t groups = kPacked[variant] ? (count + 1) / 2 : count;
-    const uint32_t sup = 8 * blocks_per_pack(kPacked[variant] ? 2 * gpb : gpb);
-    const dim3 grid(((groups + gpb - 1) / gpb + sup - 1) / sup * sup);
-    const FillPath fp = fill_path(variant, codes, ld_max, sc, *fx.o, fx.bail != nullptr);
-    hipError_t e = hipSuccess;
-    switch (variant) {
-        case 0: fill_i32<16, 10>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
-        case 1: fill_i32<16, 16>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
-        case 2: fill_i32<64, 8>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h, res, cig, sc, codes, ld_max); break;
-        case 3: return hipErrorInvalidValue;  // stripes: launch_fill_stripes
-        case 4: e = fill_pk<8, 19>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
-        case 5: e = fill_pk<16, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
-        case 7: e = fill_pk<16, 10>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
-        case 8: e = fill_pk<64, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
-        default: e = fill_pk<32, 16>(grid, stream, pairs, first, count, qs, ds, mask, end_h, res, cig, sc, codes, ld_max, fp, fx); break;
-    }
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    return dispatch_variant(variant, [&](auto g_c, auto k_c, auto v_c) -> hipError_t {
+        constexpr int G = decltype(g_c)::value, K = decltype(k_c)::value, V = decltype(v_c)::value;
+        if constexpr (V == kStripeVariant) return hipErrorInvalidValue;  // launch_fill_stripes
+        else {
+            constexpr bool kPk = kVariantTable[V].packed;
+            const dim3 grid((uint32_t)packed_blocks(G, count, kPk ? 2 : 1));
+            hipError_t e;
+            if constexpr (kPk)
+                e = fill_pk<G, K>(grid, stream, pairs, first, count, qs, ds, mask, end_h, sc, codes,
+                                  ld_max, fill_path(V, codes, ld_max, sc, *fx.o, fx.bail != nullptr),
+                                  fx);
+            else
+                e = fill_i32<G, K>(grid, stream, pairs, first, count, qs, ds, mask, scratch, end_h,
+                                   sc, codes, ld_max);
+            return e != hipSuccess ? e : hipGetLastError();
+        }
+    });
 }
 
-template <int G, int K, bool kNib = false>
-static void tb_lds(hipStream_t s, const NwPairDesc *pairs, uint32_t first, uint32_t n,
-                   const uint8_t *mask, const int32_t *end_h, uint32_t *ops, saln_nw_result *res,
-                   uint32_t *cig, Scoring sc, const uint8_t *qs, uint32_t waves = 0) {
-    constexpr uint32_t nt = tb_lds_threads<G, K, kNib>();
-    uint32_t blocks = (n + nt - 1) / nt;
-    if (waves) blocks = std::min(blocks, std::max(1u, waves / (nt / 64u)));
-    nw_traceback_lds_kernel<G, K, kNib><<<dim3(blocks), dim3(nt), 0, s>>>(
-        pairs, first, n, mask, end_h, ops, res, cig, sc, qs);
+// The cooperative walker's launches: kCoopLoaders waves per block (one walks,
+// all load its windows).  coop_window: the dynamic LDS of `rows`-row windows
+// in layout kLay (kLay 2: the window's sequence bytes, 272 + rows + 8, beside
+// it), once the kernel may use the whole 160 KB.
+constexpr int kCoopLoaders = 4;
+// speculative and span walks: a stripe walk from its right edge needs ~256 +
+// kCoopSlack rows: two blocks per CU
+constexpr int32_t kSpecRows = 296;
+template <int kLay, bool kSpec>
+static hipError_t coop_window(int32_t rows, size_t *lds) {
+    constexpr int32_t kSkew = kLay == 1 ? 127 : kLay == 2 ? 0 : 63;
+    *lds = (size_t)(rows + kSkew + 1) * kCoopLine + 16 + (kLay == 2 ? 272 + (size_t)rows + 16 : 0);
+    static const hipError_t attr = hipFuncSetAttribute(
+        (const void *)nw_traceback_coop_kernel<kCoopLoaders, kLay, kSpec>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return attr;
 }
 
 // Traceback of plan range [first, first+n).  variant >= 0: all pairs of that
@@ -3648,63 +3486,56 @@ hipError_t launch_traceback(int variant, const NwPairDesc *pairs, uint32_t first
                             uint32_t *cigar, Scoring sc, int stripe_layout, hipStream_t stream,
                             const uint32_t *spec_done, bool nib, uint32_t walk_waves) {
     if (n == 0) return hipSuccess;
-    const dim3 grid((n + 255) / 256);
-    if (nib && variant != 4 && variant != 7) return hipErrorInvalidValue;
-    switch (variant) {
-        case 0: tb_lds<16, 10>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        case 1: tb_lds<16, 16>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        case 2: tb_lds<64, 8>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        case 3: {  // column-stripe pairs: one cooperative wave per pair
-            // a few pairs: the whole 160 KB (fewer window reloads); batches:
-            // 48 KB windows, three waves per CU
-            constexpr int kLoaders = 4;  // waves per pair: one walks, all load its windows
+    if (nib && !(variant_in_range(variant) && variant_nib(variant))) return hipErrorInvalidValue;
+    if (variant < 0) {  // empty-side pairs
+        GeomTable gt;
+        for (int v = 0; v < kNumVariants; ++v) gt.g[v] = kVariantTable[v].g;
+        nw_traceback_kernel<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(
+            pairs, first, n, qs, ds, mask, end_h, results, cigar, sc, gt);
+        return hipGetLastError();
+    }
+    const hipError_t e = dispatch_variant(variant, [&](auto g_c, auto k_c, auto v_c) -> hipError_t {
+        constexpr int G = decltype(g_c)::value, K = decltype(k_c)::value, V = decltype(v_c)::value;
+        auto walk = [&](auto nib_c, uint32_t waves) {  // the LDS walker, a lane per pair
+            constexpr bool kNib = decltype(nib_c)::value;
+            constexpr uint32_t nt = tb_lds_threads<G, K, kNib>();
+            uint32_t blocks = (n + nt - 1) / nt;
+            if (waves) blocks = std::min(blocks, std::max(1u, waves / (nt / 64u)));
+            nw_traceback_lds_kernel<G, K, kNib><<<dim3(blocks), dim3(nt), 0, stream>>>(
+                pairs, first, n, mask, end_h, ops, results, cigar, sc, qs);
+            return hipSuccess;
+        };
+        (void)walk;
+        if constexpr (V == kStripeVariant) {  // column-stripe pairs: one cooperative wave per pair
+            // a few pairs: the whole 160 KB (fewer window reloads; 632 lines
+            // less the layout's skew); batches: 48 KB windows, three waves per CU
             auto go = [&](auto lay_c) -> hipError_t {
                 constexpr int kLay = decltype(lay_c)::value;
-                constexpr int32_t kSkew = kLay == 1 ? 127 : kLay == 2 ? 0 : 63;
-                static const hipError_t attr = hipFuncSetAttribute(
-                    (const void *)nw_traceback_coop_kernel<kLoaders, kLay>,
-                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                const int32_t rows = n <= 256 ? (kLay == 2 ? 628 : 632 - 128) : 128;
+                size_t lds;
+                const hipError_t attr = coop_window<kLay, false>(rows, &lds);
                 if (attr != hipSuccess) return attr;
-                // kLay 2: the window's sequence bytes (272 + rows + 8) beside it
-                const int32_t rows = n <= 256 ? (kLay == 2 ? 628 : 632 - (kSkew + 1)) : 128;
-                const size_t seq = kLay == 2 ? 272 + (size_t)rows + 16 : 0;
-                nw_traceback_coop_kernel<kLoaders, kLay>
-                    <<<dim3(n), dim3(64 * kLoaders),
-                       (size_t)(rows + kSkew + 1) * kCoopLine + 16 + seq, stream>>>(
+                nw_traceback_coop_kernel<kCoopLoaders, kLay>
+                    <<<dim3(n), dim3(64 * kCoopLoaders), lds, stream>>>(
                         pairs, first, mask, end_h, results, cigar, sc, rows, qs, ds,
                         SpecArgs{nullptr, nullptr, nullptr, nullptr, spec_done, 0});
                 return hipSuccess;
             };
-            const hipError_t e = stripe_layout == 1   ? go(std::integral_constant<int, 1>{})
-                                 : stripe_layout == 2 ? go(std::integral_constant<int, 2>{})
-                                                      : hipErrorInvalidValue;
-            if (e != hipSuccess) return e;
-            break;
-        }
-        case 4:  // 8 x 19 groups: 4-bit codes only (byte segments would not fit a slot)
-            if (!nib) return hipErrorInvalidValue;
-            tb_lds<8, 19, true>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs,
-                                walk_waves);
-            break;
-        case 5: tb_lds<16, 16>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        case 6: tb_lds<32, 16>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        case 7:
-            // (a lane per pair: two per lane made both 16 x 10 walks slower
+            return stripe_layout == 1 ? go(IntC<1>{}) : stripe_layout == 2 ? go(IntC<2>{}) : hipErrorInvalidValue;
+        } else if constexpr (V == kNarrowVariant) {
+            // 8 x 19 groups: 4-bit codes only (byte segments would not fit a slot)
+            return nib ? walk(std::true_type{}, walk_waves) : hipErrorInvalidValue;
+        } else {
+            // (16 x 10: a lane per pair: two per lane made both walks slower
             // beside the next fill - the 4-bit one in round 5, the full-code
             // one 1.367-1.384 -> 1.429-1.433 ms per step in round 6,
             // profiles/r06_full_walk_ab.jsonl)
-            if (nib) tb_lds<16, 10, true>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs);
-            else tb_lds<16, 10>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs);
-            break;
-        case 8: tb_lds<64, 16>(stream, pairs, first, n, mask, end_h, ops, results, cigar, sc, qs); break;
-        default: {  // empty-side pairs
-            GeomTable gt;
-            for (int v = 0; v < kNumVariants; ++v) gt.g[v] = kVariants[v];
-            nw_traceback_kernel<<<grid, dim3(256), 0, stream>>>(pairs, first, n, qs, ds, mask,
-                                                                end_h, results, cigar, sc, gt);
+            if constexpr (kVariantTable[V].nib)
+                if (nib) return walk(std::true_type{}, 0);
+            return walk(std::false_type{}, 0);
         }
-    }
-    return hipGetLastError();
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_traceback_spec(const NwPairDesc *pairs, SpecArgs sa, uint32_t n_blocks,
@@ -3714,30 +3545,21 @@ hipError_t launch_traceback_spec(const NwPairDesc *pairs, SpecArgs sa, uint32_t 
                                  Scoring sc, int stripe_layout, uint32_t *strict_err,
                                  hipStream_t stream) {
     if (n_blocks == 0 || passes < 1) return hipSuccess;
-    constexpr int kLoaders = 4;
-    // a stripe walk from its right edge needs ~256 + kCoopSlack rows: two
-    // blocks per CU
-    constexpr int32_t rows = 296;
     auto go = [&](auto lay_c) -> hipError_t {
         constexpr int kLay = decltype(lay_c)::value;
-        constexpr int32_t kSkew = kLay == 1 ? 127 : kLay == 2 ? 0 : 63;
-        const size_t lds = (size_t)(rows + kSkew + 1) * kCoopLine + 16 +
-                           (kLay == 2 ? 272 + (size_t)rows + 16 : 0);
-        static const hipError_t attr = hipFuncSetAttribute(
-            (const void *)nw_traceback_coop_kernel<kLoaders, kLay, true>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        size_t lds;
+        const hipError_t attr = coop_window<kLay, true>(kSpecRows, &lds);
         if (attr != hipSuccess) return attr;
         for (int k = 1; k <= passes; ++k) {
             sa.pass = k;
-            nw_traceback_coop_kernel<kLoaders, kLay, true>
-                <<<dim3(n_blocks), dim3(64 * kLoaders), lds, stream>>>(
-                    pairs, 0, mask, end_h, results, cigar, sc, rows, qs, ds, sa);
+            nw_traceback_coop_kernel<kCoopLoaders, kLay, true>
+                <<<dim3(n_blocks), dim3(64 * kCoopLoaders), lds, stream>>>(
+                    pairs, 0, mask, end_h, results, cigar, sc, kSpecRows, qs, ds, sa);
         }
         return hipGetLastError();
     };
-    const hipError_t e = stripe_layout == 1   ? go(std::integral_constant<int, 1>{})
-                         : stripe_layout == 2 ? go(std::integral_constant<int, 2>{})
-                                              : hipErrorInvalidValue;
+    const hipError_t e =
+        stripe_layout == 1 ? go(IntC<1>{}) : stripe_layout == 2 ? go(IntC<2>{}) : hipErrorInvalidValue;
     if (e != hipSuccess) return e;
     sa.pass = passes;
     nw_spec_link_kernel<<<dim3(n_spec_pairs), dim3(256), 0, stream>>>(pairs, sa, done, end_h,
@@ -3754,17 +3576,13 @@ hipError_t launch_traceback_spec(const NwPairDesc *pairs, SpecArgs sa, uint32_t 
 hipError_t launch_span_walk(const NwPairDesc *pairs, SpecArgs sa, const uint8_t *qs,
                             const uint8_t *ds, const uint8_t *mask, const int32_t *end_h,
                             Scoring sc, hipStream_t stream) {
-    constexpr int kLoaders = 4;
-    constexpr int32_t rows = 296;
-    const size_t lds = (size_t)(rows + 1) * kCoopLine + 16 + 272 + (size_t)rows + 16;
-    static const hipError_t attr = hipFuncSetAttribute(
-        (const void *)nw_traceback_coop_kernel<kLoaders, 2, true>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    size_t lds;
+    const hipError_t attr = coop_window<2, true>(kSpecRows, &lds);
     if (attr != hipSuccess) return attr;
     sa.pass = 2;
     sa.span = 1;
-    nw_traceback_coop_kernel<kLoaders, 2, true><<<dim3(1), dim3(64 * kLoaders), lds, stream>>>(
-        pairs, 0, mask, end_h, nullptr, nullptr, sc, rows, qs, ds, sa);
+    nw_traceback_coop_kernel<kCoopLoaders, 2, true><<<dim3(1), dim3(64 * kCoopLoaders), lds, stream>>>(
+        pairs, 0, mask, end_h, nullptr, nullptr, sc, kSpecRows, qs, ds, sa);
     return hipGetLastError();
 }
 
@@ -3774,18 +3592,15 @@ hipError_t launch_span_walk(const NwPairDesc *pairs, SpecArgs sa, const uint8_t 
 hipError_t launch_span_spec(const NwPairDesc *pairs, SpecArgs sa, uint32_t n_blocks, int passes,
                             const uint8_t *qs, const uint8_t *ds, const uint8_t *mask,
                             const int32_t *end_h, Scoring sc, hipStream_t stream, int pass_lo) {
-    constexpr int kLoaders = 4;
-    constexpr int32_t rows = 296;
-    const size_t lds = (size_t)(rows + 1) * kCoopLine + 16 + 272 + (size_t)rows + 16;
-    static const hipError_t attr = hipFuncSetAttribute(
-        (const void *)nw_traceback_coop_kernel<kLoaders, 2, true>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    size_t lds;
+    const hipError_t attr = coop_window<2, true>(kSpecRows, &lds);
     if (attr != hipSuccess) return attr;
     sa.span = 0;  // every stripe stops at its own left edge
     for (int k = pass_lo; k <= passes; ++k) {
         sa.pass = k;
-        nw_traceback_coop_kernel<kLoaders, 2, true><<<dim3(n_blocks), dim3(64 * kLoaders), lds, stream>>>(
-            pairs, 0, mask, end_h, nullptr, nullptr, sc, rows, qs, ds, sa);
+        nw_traceback_coop_kernel<kCoopLoaders, 2, true>
+            <<<dim3(n_blocks), dim3(64 * kCoopLoaders), lds, stream>>>(
+                pairs, 0, mask, end_h, nullptr, nullptr, sc, kSpecRows, qs, ds, sa);
     }
     return hipGetLastError();
 }
@@ -3945,38 +3760,30 @@ hipError_t launch_fill_stripes(const NwPairDesc *pairs, const uint2 *work, uint3
             const uint32_t nw = n_work * (4 / kK);
             const bool lone = o[Opt::RowsLone] && nw <= device_simds();
             const uint32_t run = (nw + 7) / 8;
-            if (lone && o[Opt::RowsXcd] && nw >= 16 && xcd_fit(stream, run, nw)) {
-                nw_fill_rows_kernel<kK, kC, kP, kPlaceXcd><<<dim3(8 * run), block, 0, stream>>>(
-                    pairs, work, qs, ds, mask, scratch, err, end_h, sc, nw, run, epoch);
-            } else if (lone) {
-                nw_fill_rows_kernel<kK, kC, kP, kPlaceLone><<<dim3(nw), block, 0, stream>>>(
-                    pairs, work, qs, ds, mask, scratch, err, end_h, sc, nw, 0, 0);
-            } else {
-                nw_fill_rows_kernel<kK, kC, kP, kPlaceShared><<<dim3(nw), block, 0, stream>>>(
-                    pairs, work, qs, ds, mask, scratch, err, end_h, sc, nw, 0, 0);
-            }
+            auto rows = [&](auto place_c, uint32_t blocks, uint32_t xcd_run, uint32_t xcd_epoch) {
+                nw_fill_rows_kernel<kK, kC, kP, decltype(place_c)::value><<<dim3(blocks), block, 0, stream>>>(
+                    pairs, work, qs, ds, mask, scratch, err, end_h, sc, nw, xcd_run, xcd_epoch);
+            };
+            if (lone && o[Opt::RowsXcd] && nw >= 16 && xcd_fit(stream, run, nw))
+                rows(IntC<kPlaceXcd>{}, 8 * run, run, epoch);
+            else if (lone) rows(IntC<kPlaceLone>{}, nw, 0, 0);
+            else rows(IntC<kPlaceShared>{}, nw, 0, 0);
         };
-        auto by_k = [&](auto codes_c, auto minpen_c) {
-            if (rows_k == 2) go(std::integral_constant<int, 2>{}, codes_c, minpen_c);
-            else go(std::integral_constant<int, 1>{}, codes_c, minpen_c);
-        };
-        auto by_codes = [&](auto minpen_c) {
-            if (codes == kCodesFull) by_k(std::integral_constant<int, kCodesFull>{}, minpen_c);
-            else if (codes == kCodesNone) by_k(std::integral_constant<int, kCodesNone>{}, minpen_c);
-            else by_k(std::integral_constant<int, kCodesWalk>{}, minpen_c);
-        };
-        if (pm >= 0 && pm <= 256) by_codes(std::true_type{});
-        else by_codes(std::false_type{});
-        return hipGetLastError();
+        const hipError_t e = dispatch_codes(codes, [&](auto codes_c) {
+            return dispatch_bool(pm >= 0 && pm <= 256, [&](auto minpen_c) {
+                if (rows_k == 2) go(IntC<2>{}, codes_c, minpen_c);
+                else go(IntC<1>{}, codes_c, minpen_c);
+                return hipSuccess;
+            });
+        });
+        return e != hipSuccess ? e : hipGetLastError();
     }
     if (!pk) return hipErrorInvalidValue;  // (round 1's skewed i32 stripes are retired)
-    if (codes == kCodesFull)
-        nw_fill_stripe_pk_kernel<kCodesFull><<<grid, block, 0, stream>>>(pairs, work, qs, ds, mask, scratch, prog, err, end_h, sc);
-    else if (codes == kCodesNone)
-        nw_fill_stripe_pk_kernel<kCodesNone><<<grid, block, 0, stream>>>(pairs, work, qs, ds, mask, scratch, prog, err, end_h, sc);
-    else
-        nw_fill_stripe_pk_kernel<kCodesWalk><<<grid, block, 0, stream>>>(pairs, work, qs, ds, mask, scratch, prog, err, end_h, sc);
-    return hipGetLastError();
+    return dispatch_codes(codes, [&](auto codes_c) {
+        nw_fill_stripe_pk_kernel<decltype(codes_c)::value><<<grid, block, 0, stream>>>(
+            pairs, work, qs, ds, mask, scratch, prog, err, end_h, sc);
+        return hipGetLastError();
+    });
 }
 
 // Host path: pack each pair's CIGAR words (capacity-spaced at src_off) densely
@@ -4000,121 +3807,6 @@ hipError_t launch_cigar_compact(const saln_nw_result *res, const uint64_t *src_o
     nw_cigar_compact_kernel<<<dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, stream>>>(
         res, src_off, dst_off, src, dst, n);
     return hipGetLastError();
-}
-
-Geom variant_geom(int v) { return kVariants[v]; }
-
-// The packed stripe fill holds a row relative to the stripe's left input:
-// within 256 columns of it values span 256 * (2|m| + 4|ge|) plus the gap
-// and penalty offsets of M / I / D (see nw_fill_stripe_pk_kernel).
-// The packed stripe fill: its 128-virtual-lane chain doubles a stripe's skew,
-// so one long pair (C4, 391 waves alone on their SIMDs) fills slower (45.4 vs
-// 40.1 ms) although the step is cheaper; once the stripe waves fill the chip
-// it wins (400 x 5 kbp pairs: 8.0 vs 9.2 ms end to end).  Chosen per plan
-// from the stripe-wave count; option nw.stripe_pk = 0 / 1 forces it.
-// Row-fill columns per lane: K = 1 (64-column stripes) while every stripe
-// wave of the plan has a SIMD to itself (a shorter row step: C1 0.197 ->
-// 0.188 ms, 5 kbp 0.75 -> 0.70 ms), else K = 2 (C4: 1,564 K = 1 waves share
-// SIMDs, 19.5 vs 14.5 ms).  Option nw.rows_k = 1, 2 or 4 forces it (read per
-// plan).
-int stripe_rows_k(uint64_t waves_k1, const Options &o) {
-    if (const int64_t v = o[Opt::RowsK]) return v == 1 ? 1 : 2;
-    return waves_k1 <= 1024 ? 1 : 2;
-}
-
-bool stripe_packed(const Scoring &sc, uint64_t n_waves, bool wide, const Options &o) {
-    const int64_t force = o[Opt::StripePk];  // -1 auto
-    if (force == 0) return false;
-    if (force != 1 && (n_waves < kStripePkMinWaves || !wide)) return false;
-    const int64_t pen = 2ll * (sc.match - sc.mismatch);
-    if (pen < 2 || pen > 32 || sc.gap_extend > 0 || sc.gap_open > 0) return false;
-    const int64_t m = std::abs(sc.match), ge = std::abs(sc.gap_extend), go = std::abs(sc.gap_open);
-    return 256 * (2 * m + 4 * ge) + 4 * (go + ge) + 2 * pen + 512 < 30000;
-}
-bool variant_packed(int v) { return kPacked[v]; }
-
-// Packed i16 is exact while every value and every same-cell difference stays
-// inside int16 with the position offsets of nw_fill_pk_kernel (see there):
-// `rows` rows of growth a and lq columns of growth b from the frame's origin.
-static bool packed_range_ok(uint32_t lq, uint32_t rows, const Scoring &sc) {
-    const int64_t pen = 2ll * (sc.match - sc.mismatch);
-    // pen >= 2: the q==d bit comes from the penalty (0 or pen in each half)
-    if (pen < 2 || pen > 32 || sc.gap_extend > 0 || sc.gap_open > 0) return false;
-    const int64_t span = std::max<int64_t>(
-        {std::abs(sc.match), std::abs(sc.mismatch), std::abs(sc.gap_open) + std::abs(sc.gap_extend)});
-    const int64_t a = 2 * (std::abs(sc.match) + std::abs(sc.gap_extend)) + 2 * span;
-    return (int64_t)rows * a + (int64_t)lq * (2 * std::abs(sc.gap_extend) + 2 * span) + 256 < 30000;
-}
-static bool packed_ok(uint32_t lq, uint32_t ld, const Scoring &sc) {
-    return packed_range_ok(lq, ld, sc);
-}
-// One int16 frame holds a launch of G-lane groups of W columns whose longest
-// db has `ld` rows: the values of all W columns (a launch decides its frame
-// from the group's width, not from a pair's own query) and the 32-bit staged
-// db rows (kPackedLdsMax; under small penalties the value range alone admits
-// more rows than the LDS holds).  choose_variant and the launches share it, so
-// a pair is never handed to a frame that no guard accepted for it.
-static bool packed_single_ok(uint32_t G, uint32_t W, uint32_t ld, const Scoring &sc) {
-    return packed_ok(W, ld, sc) && (size_t)(256 / G) * (ld + 2 * G) * 4 <= kPackedLdsMax;
-}
-// The rebasing fill (kRebase).  At step t a lane's value is
-// X~(r,c) - drift * r0 with r in [r0 - G, r0 + kRebaseSteps) and
-//   X~(r,c) - drift*r0 = [X~(r,c) - X~(r,0)] + [X~(r,0) - drift*r] + drift*(r - r0):
-// the first term lies in [2*go, c*(2|m| + 4|ge|)] (a row's H exceeds its
-// column-0 value by at most c*(m - ge), the c columns' diagonal gain over the
-// gap it replaces, and falls below it by at most a gap; beta*c on top), the
-// second is the constant 2*(go + ge) + 1 while hs_col0 is linear (ld <= 4096
-// and |go| + 4097*|ge| < 2^15: the sentinel floor is not reached), the third
-// is at most |drift| * (period + G).  M / I / D sit within an open + extend +
-// penalty of H.  The db length is also bounded by the staged rows
-// (kPackedLdsMax).
-static bool packed_ok_rebase(uint32_t lq, uint32_t ld, const Scoring &sc, uint32_t G, uint32_t W) {
-    const int64_t pen = 2ll * (sc.match - sc.mismatch);
-    if (pen < 2 || pen > 32 || sc.gap_extend > 0 || sc.gap_open > 0 || lq > W) return false;
-    const uint32_t gpb = 256 / G;
-    if ((size_t)gpb * (ld + 2 * G) * 2 > kPackedLdsMax || ld > 4096) return false;  // 16-bit rows
-    const int64_t m = std::abs(sc.match), ge = std::abs(sc.gap_extend), go = std::abs(sc.gap_open);
-    if (go + 4097 * ge >= 32768) return false;
-    const int64_t drift = std::abs(2 * sc.gap_extend - 2 * sc.match + 2 * sc.gap_extend);
-    // column term [-(2go + 1), W*(2m + 4ge) + 2(go + ge)] centred by rebase_center
-    const int64_t col = (int64_t)W * (2 * m + 4 * ge);
-    const int64_t half = std::max<int64_t>(col - rebase_center(sc, (int32_t)W), rebase_center(sc, (int32_t)W));
-    const int64_t bound = half + (kRebaseSteps + (int64_t)G) * drift + 4 * (go + ge) + 2 * pen + 512;
-    return bound < 30000;
-}
-
-int choose_variant(uint32_t len_q, uint32_t len_db, const Scoring &sc, bool narrow) {
-    // the packed fills carry V' = 2V + p (no alive flag): sentinel-free pairs only
-    const bool free = sentinel_free(sc, len_q, len_db);
-    if (!free) return len_q <= 160 ? 0 : len_q <= 256 ? 1 : len_q <= 512 ? 2 : 3;
-    // 8 x 19 groups (4-bit walk codes): queries of <= 152 columns, one
-    // int16 frame or the rebasing one (launch_fill decides from the widest)
-    if (narrow && len_q <= 152) {
-        const Geom g = kVariants[4];
-        if (packed_single_ok(g.G, g.W(), len_db, sc) ||
-            packed_ok_rebase(len_q, len_db, sc, g.G, g.W()))
-            return 4;
-    }
-    // one int16 frame, judged as the launch judges it: over the whole width of
-    // the variant's lane groups (a query narrower than its group once passed
-    // here on its own width, and the launch then took the rebasing frame for
-    // it without packed_ok_rebase having been asked)
-    if (len_q <= 512) {
-        const int v = len_q <= 160 ? 7 : len_q <= 256 ? 5 : 6;
-        if (packed_single_ok(kVariants[v].G, kVariants[v].W(), len_db, sc)) return v;
-    }
-    // longer db: the same packed variants with a rebasing int16 frame; 513 to
-    // 1,024 query columns in 64-lane groups (narrower queries would leave
-    // most of those lanes idle: the i32 lanes are faster for them)
-    for (const int v : {7, 5, 6}) {
-        const Geom g = kVariants[v];
-        if (len_q <= g.W() && packed_ok_rebase(len_q, len_db, sc, g.G, g.W())) return v;
-    }
-    if (len_q > 512 && packed_ok_rebase(len_q, len_db, sc, 64, 1024)) return 8;
-    if (len_q <= 160) return 0;
-    if (len_q <= 256) return 1;
-    if (len_q <= 512) return 2;
-    return 3;  // column stripes, one wave each (nw_fill_stripe_kernel)
 }
 
 }  // namespace saln

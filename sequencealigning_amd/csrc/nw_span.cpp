@@ -306,7 +306,7 @@ int saln_nw_span_fill(saln_nw_span *s, const uint8_t *d_q, const uint8_t *d_db, 
     HIP_TRY(hipSetDevice(s->ctx->device));
     HIP_TRY(launch_fill_stripes(s->d_pair, s->d_work, s->n_work, d_q, d_db, s->mask_arg(),
                                 s->scratch_arg(), nullptr, s->d_err, s->d_endh, s->sc,
-                                0 /* walk codes */, 2 /* row-major tiles */, s->K,
+                                kCodesWalk, 2 /* row-major tiles */, s->K,
                                 resolve_stream(stream, s->ctx), s->opts, ++s->fill_epoch));
     return SALN_OK;
 }
