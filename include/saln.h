@@ -44,7 +44,7 @@ typedef enum {
     SALN_ENUM_CAP = 6,           /* NW co-optimal enumeration hit the caller's cap */
     SALN_SPAN_UNLINKED = 7,      /* saln_nw_spans_walk only: the speculative passes did not
                                     link; walk span by span (saln_nw_span_walk) */
-    SALN_TRACE_CAP = 8,          /* saln_wfa_affine_align_batch: the pair's trace codes alone
+    SALN_TRACE_CAP = 8,          /* saln_wfa_affine_align_batch, saln_ends_free_align_batch: the pair's trace codes alone
                                     exceed trace_budget_bytes; score only, no CIGAR */
     SALN_INTERNAL = 9,           /* saln_wfa_affine_align_batch: the trace pass disagreed with
                                     the score pass (internal inconsistency; never expected) */
@@ -701,6 +701,104 @@ typedef struct {
 int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t *len_q,
                                   const uint64_t *len_db, uint64_t n_pairs,
                                   saln_wfa_affine_pass_geometry out[2]);
+
+/* ------------------------------- ends-free alignment: local and semi-global (new)
+ * NOT a reference-parity path.  The reference only declares these modes:
+ * ScoreTensor::Local and ::SemiGlobal carry empty comments where the fill
+ * should be (needleman_wunsch_affine.rs:238-239, :331-332) and n_w_align
+ * answers "not implemented" (:433-434), which saln_nw_* and the CLI keep
+ * doing.  These entry points compute what the two modes are meant to: Gotoh
+ * affine-gap alignment with free ends, on the GPU (ends_free_kernels.hip),
+ * checked against the plain model tests/ends_free_model.py.
+ *
+ * Orientation, CIGAR words and scoring as above: q = query = columns j
+ * (length n), d = db = rows i (length m), the db is the reference sequence;
+ * a gap of length L costs gap_open + L * gap_extend; bases compare as bytes.
+ * This engine takes match > 0, mismatch < 0, gap_open <= 0, gap_extend < 0
+ * and refuses a batch with a pair for which (n + m + 2) * max|parameter| >=
+ * 2^30 (SALN_E_INVALID).  Gaps open from M only (an I run and a D run are
+ * never adjacent), s(i, j) is match or mismatch of d[i-1] against q[j-1]:
+ *   I(i,j) = max(I(i,j-1) + e, M(i,j-1) + o + e)      j >= 1
+ *   D(i,j) = max(D(i-1,j) + e, M(i-1,j) + o + e)      i >= 1
+ *   M(i,j) = s(i,j) + P(i-1,j-1)                      i, j >= 1
+ *   P = max(M, I, D) (semi-global), max(0, M, I, D) (local);
+ * everything no rule gives is -infinity.
+ *  - SALN_MODE_SEMI_GLOBAL: the whole query against a free db substring.
+ *    M(i,0) = 0 for every i (the start); M(0,j>0), I(i,0), D(i,0), D(0,j) are
+ *    -infinity.  score = max over i in 0..m of max(M(i,n), I(i,n)); the
+ *    smallest i wins a tie, M before I.  n = 0: score 0, no words, db_begin =
+ *    db_end = 0.  m = 0: gap_open + n * gap_extend and the single word nI.
+ *    q_begin = 0 and q_end = n always.
+ *  - SALN_MODE_LOCAL: score = max(0, max over i, j of M(i,j)); the alignment
+ *    begins and ends with an M column; the smallest i, then the smallest j,
+ *    wins a tie.  Score 0: no words, all four coordinates 0.
+ * The walk's choice among co-optimal paths is fixed.  In M at (i,j): emit
+ * '=' or 'X', v = M(i,j) - s(i,j), go to (i-1,j-1); local stops when v == 0,
+ * semi-global on reaching column 0; else the next state is the first of M,
+ * I, D whose value there equals v.  In I or D extend comes before open.  A
+ * pair's words depend on nothing but the pair and the scoring.
+ * Ranges are half-open and 0-based: the '=', 'X' and 'I' lengths sum to
+ * q_end - q_begin, the '=', 'X' and 'D' lengths to db_end - db_begin.
+ *
+ * Limits: a query of at most 1,024 columns (one chunk of the lane fill;
+ * saln_ends_free_pair_geometry reports its class) and a db of at most 65,000
+ * rows (a group's db row is staged in LDS); a longer sequence makes the batch
+ * SALN_E_INVALID with a message naming the limit. */
+typedef struct {
+    int32_t score, status;            /* SALN_OK | SALN_TRACE_CAP */
+    int32_t q_begin, q_end, db_begin, db_end;   /* begins -1 when no walk ran */
+    uint32_t cigar_len, reserved;
+} saln_ends_free_result;              /* 32 bytes */
+
+/* Pair conventions and argument errors as saln_wfa_affine_align_batch (NULL
+ * pair lists = all-vs-all, db outer).  mode: SALN_MODE_LOCAL or
+ * SALN_MODE_SEMI_GLOBAL; SALN_MODE_GLOBAL is SALN_E_INVALID (use saln_nw_*).
+ * want_cigar != 0: the fill stores 4-bit trace codes and the walk follows
+ * them, in chunks: pairs are packed greedily in pair order into chunks of at
+ * most trace_budget_bytes of codes (saln_ends_free_trace_bytes each; 0
+ * selects 1 GiB).  A pair whose codes alone exceed the budget has its score
+ * and end coordinates, status SALN_TRACE_CAP, begins -1 and no words.
+ * want_cigar == 0 runs the fill only (no codes stored): score and ends, begins
+ * -1, cigar_len 0.  The handle owns the words. */
+typedef struct saln_ends_free_aln saln_ends_free_aln;
+int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                               uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                               uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                               uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                               uint64_t trace_budget_bytes, int want_cigar,
+                               saln_ends_free_aln **out);
+uint64_t saln_ends_free_aln_count(const saln_ends_free_aln *a);
+/* res and cigar are optional.  cigar points into the handle, res->cigar_len
+ * words, valid until saln_ends_free_aln_free; the words of consecutive pairs
+ * are contiguous, in pair order. */
+int saln_ends_free_aln_get(const saln_ends_free_aln *a, uint64_t pair, saln_ends_free_result *res,
+                           const uint32_t **cigar);
+void saln_ends_free_aln_free(saln_ends_free_aln *a);
+
+/* Device-resident score-only form: plan from host offsets and a pair list
+ * (NULL = all-vs-all), execute on device sequences (same CSR layout) into
+ * device results[n_pairs] (score, ends, begins -1).  Stream as the other
+ * plans (NULL = the context's own stream). */
+typedef struct saln_ends_free_plan saln_ends_free_plan;
+int saln_ends_free_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                               const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                               const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                               const saln_nw_scoring *scoring, saln_ends_free_plan **out);
+int saln_ends_free_execute(saln_ends_free_plan *plan, const uint8_t *d_q_seq,
+                           const uint8_t *d_db_seq, saln_ends_free_result *d_results, void *stream);
+int saln_ends_free_plan_destroy(saln_ends_free_plan *plan);
+
+/* Host only (no device needed): bytes of trace codes of one pair, the one
+ * place the size is computed: len_db rows of ceil(len_q / cols) * cols / 2
+ * bytes (4 bits per cell; cols: the pair's class, below), rounded up to a
+ * multiple of 8; 0 when a sequence is empty.  SALN_E_INVALID above the
+ * engine's limits. */
+int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes);
+/* Host only: the class a query of len_q columns runs in: one pair per group
+ * of *lanes lanes, *cols_per_lane query columns per lane (16 x 10, 16 x 16,
+ * 64 x 8, 64 x 16: the smallest that holds the query).  SALN_E_INVALID above
+ * 1,024 columns.  The launch code asks the same function. */
+int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols_per_lane);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

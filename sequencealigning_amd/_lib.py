@@ -104,6 +104,17 @@ class WfaAffinePassGeometry(C.Structure):
 WFA_AFFINE_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("cigar_len", "<u4"),
                            ("reserved", "<u4")]
 
+class EndsFreeResult(C.Structure):
+    """saln_ends_free_result: one pair of the ends-free engine (local / semi-global)."""
+    _fields_ = [("score", C.c_int32), ("status", C.c_int32), ("q_begin", C.c_int32),
+                ("q_end", C.c_int32), ("db_begin", C.c_int32), ("db_end", C.c_int32),
+                ("cigar_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ENDS_FREE_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("q_begin", "<i4"), ("q_end", "<i4"),
+                          ("db_begin", "<i4"), ("db_end", "<i4"), ("cigar_len", "<u4"),
+                          ("reserved", "<u4")]
+
 # symbols every build must export (tests check this list against include/saln.h)
 EXPORTS = [
     "saln_context_create", "saln_context_destroy", "saln_last_error", "saln_abi_version",
@@ -128,6 +139,9 @@ EXPORTS = [
     "saln_wfa_affine_plan_destroy",
     "saln_wfa_affine_align_batch", "saln_wfa_affine_aln_count", "saln_wfa_affine_aln_get",
     "saln_wfa_affine_aln_free", "saln_wfa_affine_trace_bytes", "saln_wfa_affine_plan_geometry",
+    "saln_ends_free_align_batch", "saln_ends_free_aln_count", "saln_ends_free_aln_get",
+    "saln_ends_free_aln_free", "saln_ends_free_plan_create", "saln_ends_free_execute",
+    "saln_ends_free_plan_destroy", "saln_ends_free_trace_bytes", "saln_ends_free_pair_geometry",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -272,6 +286,23 @@ def lib() -> C.CDLL:
                                                   C.c_uint64, C.c_int32, u64p]
         L.saln_wfa_affine_plan_geometry.argtypes = [C.POINTER(WfaPenalties), vp, vp, C.c_uint64,
                                                     C.POINTER(WfaAffinePassGeometry)]
+        L.saln_ends_free_align_batch.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                                 vp, C.c_uint64, C.c_int32,
+                                                 C.POINTER(NwScoring), C.c_uint64, C.c_int,
+                                                 C.POINTER(vp)]
+        L.saln_ends_free_aln_count.argtypes = [vp]
+        L.saln_ends_free_aln_count.restype = C.c_uint64
+        L.saln_ends_free_aln_get.argtypes = [vp, C.c_uint64, C.POINTER(EndsFreeResult),
+                                             C.POINTER(u32p)]
+        L.saln_ends_free_aln_free.argtypes = [vp]
+        L.saln_ends_free_aln_free.restype = None
+        L.saln_ends_free_plan_create.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                                 C.c_uint64, C.c_int32, C.POINTER(NwScoring),
+                                                 C.POINTER(vp)]
+        L.saln_ends_free_execute.argtypes = [vp, vp, vp, vp, vp]
+        L.saln_ends_free_plan_destroy.argtypes = [vp]
+        L.saln_ends_free_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
+        L.saln_ends_free_pair_geometry.argtypes = [C.c_uint64, u32p, u32p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

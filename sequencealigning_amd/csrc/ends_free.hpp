@@ -1,0 +1,79 @@
+// Ends-free engine (include/saln.h, saln_ends_free_*): what the host file
+// (ends_free_host.cpp) and the kernels (ends_free_kernels.hip) share.  The
+// device-side helpers of the fill and the walk are in ends_free_dev.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "saln.h"
+
+namespace saln {
+
+// One pair of a launch.  code_off / cig_off: the pair's trace codes (bytes)
+// and CIGAR word area (words) in the chunk's workspaces; out: its record in
+// the results array.
+struct EfPair {
+    uint64_t q_off, d_off, code_off, cig_off;
+    uint32_t lq, ld, out, row_bytes;
+};
+static_assert(sizeof(EfPair) == 48, "EfPair layout");
+
+struct EfScoring {
+    int32_t match, mismatch, open, extend;
+};
+
+// Query classes: one pair per group of `lanes` lanes, `cols` query columns per
+// lane, the whole query in one chunk (the i32 lane classes of the NW table).
+struct EfClass {
+    int32_t lanes, cols;
+};
+constexpr int kEfClasses = 4;
+constexpr EfClass kEfClass[kEfClasses] = {{16, 10}, {16, 16}, {64, 8}, {64, 16}};
+constexpr uint64_t kEfMaxQ = 1024;   // longest query (kEfClass's widest class)
+constexpr uint64_t kEfMaxDb = 65000; // longest db: a group's db row is staged in LDS
+
+// The class a query of len_q columns runs in (-1: above kEfMaxQ).  The one
+// place the decision is made: saln_ends_free_pair_geometry, the code sizes
+// and the launches all ask it.
+inline int ef_class_of(uint64_t len_q) {
+    for (int c = 0; c < kEfClasses; ++c)
+        if (len_q <= (uint64_t)kEfClass[c].lanes * (uint64_t)kEfClass[c].cols) return c;
+    return -1;
+}
+
+// Bytes of one code row of a pair (4 bits per cell): the lanes that hold a
+// query column store cols / 2 bytes each.
+inline uint32_t ef_row_bytes(uint64_t len_q) {
+    const int c = ef_class_of(len_q);
+    if (c < 0 || len_q == 0) return 0;
+    const uint64_t k = (uint64_t)kEfClass[c].cols;
+    return (uint32_t)((len_q + k - 1) / k * (k / 2));
+}
+
+// Dynamic LDS of a fill workgroup of `groups` lane groups: each group's db
+// row, padded by `lanes` bytes on both sides (the skew reads past the ends).
+inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
+    return (uint64_t)groups * ((uint64_t)ld_max + 2u * (uint32_t)kEfClass[cls].lanes);
+}
+
+// Fill of pairs[first .. first + count), all of class cls with dbs of at most
+// ld_max rows.  codes == nullptr: score only.  end_state (with codes): the
+// state of each pair's end cell (0 M, 1 I), indexed like results.
+hipError_t launch_ef_fill(int cls, bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+                          uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
+                          uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
+                          hipStream_t s);
+// Walk of pairs[0 .. count): one pair per lane, from the end cell the fill
+// reported.  A pair's words end at words[cig_off + lq + ld), cigar_len of
+// them (also in lens, indexed like pairs).
+hipError_t launch_ef_walk(bool local, const EfPair *pairs, uint32_t count, const uint8_t *qs,
+                          const uint8_t *ds, const uint8_t *codes, const uint8_t *end_state,
+                          saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
+                          hipStream_t s);
+// Packs those words: pair k's lens[k] words to out[dst[k] ..).
+hipError_t launch_ef_gather(const EfPair *pairs, uint32_t count, const uint32_t *words,
+                            const uint32_t *lens, const uint64_t *dst, uint32_t *out,
+                            hipStream_t s);
+
+}  // namespace saln

@@ -1,0 +1,390 @@
+// C ABI of the ends-free engine (include/saln.h, saln_ends_free_*): local and
+// semi-global affine-gap alignment.  Not a reference-parity path - the
+// reference only declares these modes (needleman_wunsch_affine.rs:238-239,
+// :331-332, :433-434); the checker is the plain model tests/ends_free_model.py.
+//
+// A batch's pairs are grouped by query class (ef_class_of) and, within a
+// class, ordered by falling db length and cut where the length's power-of-two
+// bucket changes: one fill launch per cut, each staging rows of its own
+// longest db.  Alignment mode packs the pairs in pair order into chunks of at
+// most trace_budget_bytes of codes; per chunk the fill with codes, the walk,
+// the words packed on the device in pair order, then the words back.  Pairs
+// whose codes alone exceed the budget run in a score-only fill of their own.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "ends_free.hpp"
+#include "host_common.hpp"
+
+using namespace saln;
+
+namespace {
+
+struct Launch {
+    int cls;
+    uint32_t first, count, ld_max;
+};
+
+int bit_bucket(uint32_t v) {
+    int b = 0;
+    while (v) ++b, v >>= 1;
+    return b;
+}
+
+// Orders pairs for the fill (class, then falling db length) and cuts them
+// into launches.
+void plan_launches(std::vector<EfPair> *pairs, std::vector<Launch> *out) {
+    std::stable_sort(pairs->begin(), pairs->end(), [](const EfPair &a, const EfPair &b) {
+        const int ca = ef_class_of(a.lq), cb = ef_class_of(b.lq);
+        return ca != cb ? ca < cb : a.ld > b.ld;
+    });
+    out->clear();
+    for (uint32_t k = 0; k < pairs->size(); ++k) {
+        const EfPair &p = (*pairs)[k];
+        const int cls = ef_class_of(p.lq);
+        if (out->empty() || out->back().cls != cls ||
+            bit_bucket(out->back().ld_max) != bit_bucket(p.ld))
+            out->push_back(Launch{cls, k, 0, p.ld});
+        ++out->back().count;
+    }
+}
+
+int check_mode(int32_t mode) {
+    if (mode == SALN_MODE_LOCAL || mode == SALN_MODE_SEMI_GLOBAL) return SALN_OK;
+    if (mode == SALN_MODE_GLOBAL)
+        set_error("ends_free: SALN_MODE_GLOBAL is not an ends-free mode; global alignment is "
+                  "saln_nw_align / saln_nw_align_batch / saln_nw_plan_create");
+    else
+        set_error("ends_free: unknown mode " + std::to_string(mode));
+    return SALN_E_INVALID;
+}
+
+int make_scoring(const saln_nw_scoring *s, EfScoring *out, uint64_t *max_abs) {
+    const EfScoring sc = s ? EfScoring{s->match, s->mismatch, s->gap_open, s->gap_extend}
+                           : EfScoring{5, -4, -8, -6};
+    if (sc.match <= 0 || sc.mismatch >= 0 || sc.open > 0 || sc.extend >= 0) {
+        set_error("ends_free: scoring {" + std::to_string(sc.match) + ", " + std::to_string(sc.mismatch) +
+                  ", " + std::to_string(sc.open) + ", " + std::to_string(sc.extend) +
+                  "} is outside this engine's domain (match > 0, mismatch < 0, gap_open <= 0, "
+                  "gap_extend < 0)");
+        return SALN_E_INVALID;
+    }
+    const auto mag = [](int32_t v) { return (uint64_t)(v < 0 ? -(int64_t)v : (int64_t)v); };
+    *max_abs = std::max({mag(sc.match), mag(sc.mismatch), mag(sc.open), mag(sc.extend)});
+    *out = sc;
+    return SALN_OK;
+}
+
+// The engine's limits for one pair (lengths, int32 range of the values).
+int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs) {
+    if (lq > kEfMaxQ) {
+        set_error("ends_free: a query of " + std::to_string(lq) + " columns is above the limit of " +
+                  std::to_string(kEfMaxQ) + " (one chunk of the lane fill)");
+        return SALN_E_INVALID;
+    }
+    if (ld > kEfMaxDb) {
+        set_error("ends_free: a db of " + std::to_string(ld) + " rows is above the limit of " +
+                  std::to_string(kEfMaxDb) + " (the db row is staged in LDS)");
+        return SALN_E_INVALID;
+    }
+    if ((lq + ld + 2) * max_abs >= (1ull << 30)) {
+        set_error("ends_free: (len_q + len_db + 2) * max|scoring parameter| reaches 2^30: the "
+                  "scores could leave the engine's int32 range");
+        return SALN_E_INVALID;
+    }
+    return SALN_OK;
+}
+
+uint64_t code_bytes(uint64_t lq, uint64_t ld) {
+    if (lq == 0 || ld == 0) return 0;
+    return (ld * ef_row_bytes(lq) + 7) & ~7ull;
+}
+
+int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
+                const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, uint64_t max_abs,
+                std::vector<EfPair> *out) {
+    out->resize(n_pairs);
+    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        uint64_t qi, di;
+        if (!pairs.at(k, &qi, &di)) return SALN_E_INVALID;
+        const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
+        const int rc = check_pair(lq, ld, max_abs);
+        if (rc != SALN_OK) return rc;
+        EfPair p{};
+        p.q_off = q_off[qi];
+        p.d_off = db_off[di];
+        p.lq = (uint32_t)lq;
+        p.ld = (uint32_t)ld;
+        p.out = (uint32_t)k;
+        p.row_bytes = ef_row_bytes(lq);
+        (*out)[k] = p;
+    }
+    return SALN_OK;
+}
+
+// The fills of `pairs` (device copy d_pairs, in plan_launches' order).
+int run_fills(const std::vector<Launch> &launches, bool local, const EfPair *d_pairs,
+              const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, uint8_t *d_codes,
+              uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s) {
+    for (const Launch &l : launches)
+        HIP_TRY(launch_ef_fill(l.cls, local, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+                               d_codes, d_end_state, d_results, s));
+    return SALN_OK;
+}
+
+}  // namespace
+
+struct saln_ends_free_plan {
+    saln_context *ctx = nullptr;
+    EfScoring sc{};
+    bool local = false;
+    uint64_t n = 0;
+    std::vector<Launch> launches;
+    DevBuf d_pairs;
+};
+
+// The result handle of saln_ends_free_align_batch: pair k's words are
+// words[off[k] .. off[k] + res[k].cigar_len).
+struct saln_ends_free_aln {
+    std::vector<saln_ends_free_result> res;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> words;
+};
+
+extern "C" {
+
+int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols_per_lane) {
+    if (!lanes || !cols_per_lane) return SALN_E_INVALID;
+    const int c = ef_class_of(len_q);
+    if (c < 0) return check_pair(len_q, 0, 0);
+    *lanes = (uint32_t)kEfClass[c].lanes;
+    *cols_per_lane = (uint32_t)kEfClass[c].cols;
+    return SALN_OK;
+}
+
+int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes) {
+    if (!bytes) return SALN_E_INVALID;
+    const int rc = check_pair(len_q, len_db, 0);
+    if (rc != SALN_OK) return rc;
+    *bytes = code_bytes(len_q, len_db);
+    return SALN_OK;
+}
+
+int saln_ends_free_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                               const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                               const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                               const saln_nw_scoring *scoring, saln_ends_free_plan **out) {
+    if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
+    if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
+    auto p = std::make_unique<saln_ends_free_plan>();
+    p->ctx = ctx;
+    p->d_pairs = DevBuf(ctx);
+    uint64_t max_abs = 0;
+    int rc = check_mode(mode);
+    if (rc == SALN_OK) rc = make_scoring(scoring, &p->sc, &max_abs);
+    std::vector<EfPair> pairs;
+    if (rc == SALN_OK)
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &pairs);
+    if (rc != SALN_OK) return rc;
+    p->local = mode == SALN_MODE_LOCAL;
+    p->n = n_pairs;
+    plan_launches(&pairs, &p->launches);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n_pairs) {
+        HIP_TRY(p->d_pairs.alloc(n_pairs * sizeof(EfPair)));
+        HIP_TRY(hipMemcpy(p->d_pairs.p, pairs.data(), n_pairs * sizeof(EfPair), hipMemcpyHostToDevice));
+    }
+    *out = p.release();
+    return SALN_OK;
+}
+
+int saln_ends_free_execute(saln_ends_free_plan *p, const uint8_t *d_q_seq, const uint8_t *d_db_seq,
+                           saln_ends_free_result *d_results, void *stream) {
+    if (!p || !d_results || !d_q_seq || !d_db_seq) return SALN_E_INVALID;
+    if (!p->n) return SALN_OK;
+    hipStream_t s = resolve_stream(stream, p->ctx);
+    HIP_TRY(hipSetDevice(p->ctx->device));
+    return run_fills(p->launches, p->local, p->d_pairs.as<EfPair>(), d_q_seq, d_db_seq, p->sc,
+                     nullptr, nullptr, d_results, s);
+}
+
+int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
+    delete p;
+    return SALN_OK;
+}
+
+int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                               uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                               uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                               uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                               uint64_t trace_budget_bytes, int want_cigar,
+                               saln_ends_free_aln **out) {
+    if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
+    if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
+    EfScoring sc{};
+    uint64_t max_abs = 0;
+    int rc = check_mode(mode);
+    if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs);
+    std::vector<EfPair> all;
+    if (rc == SALN_OK)
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all);
+    if (rc != SALN_OK) return rc;
+    const bool local = mode == SALN_MODE_LOCAL;
+    auto aln = std::make_unique<saln_ends_free_aln>();
+    aln->off.assign(n_pairs + 1, 0);
+    if (n_pairs == 0) {
+        *out = aln.release();
+        return SALN_OK;
+    }
+    aln->res.assign(n_pairs, saln_ends_free_result{});
+
+    // chunks: pairs in pair order, at most `budget` bytes of codes each; the
+    // pairs without codes (score only, or above the budget) in one more
+    const uint64_t budget = trace_budget_bytes ? trace_budget_bytes : (1ull << 30);
+    struct Chunk {
+        std::vector<EfPair> pairs;
+        uint64_t bytes = 0, words = 0;
+    };
+    std::vector<Chunk> chunks;
+    Chunk plain;
+    std::vector<uint8_t> capped(n_pairs, 0);
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        EfPair p = all[k];
+        const uint64_t bytes = code_bytes(p.lq, p.ld);
+        if (!want_cigar || bytes > budget) {
+            capped[k] = want_cigar ? 1 : 0;
+            plain.pairs.push_back(p);
+            continue;
+        }
+        if (chunks.empty() || chunks.back().bytes + bytes > budget ||
+            chunks.back().pairs.size() >= (1u << 30))
+            chunks.emplace_back();
+        Chunk &c = chunks.back();
+        p.code_off = c.bytes;
+        p.cig_off = c.words;
+        c.bytes += bytes;
+        c.words += (uint64_t)p.lq + p.ld;
+        c.pairs.push_back(p);
+    }
+    std::vector<EfPair>().swap(all);
+    uint64_t max_bytes = 0, max_words = 0, max_n = plain.pairs.size();
+    for (const Chunk &c : chunks) {
+        max_bytes = std::max(max_bytes, c.bytes);
+        max_words = std::max(max_words, c.words);
+        max_n = std::max<uint64_t>(max_n, c.pairs.size());
+    }
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;  // every launch below runs on it: the blocks sync it alone
+    DevBuf dq(ctx, s), dd(ctx, s), d_pairs(ctx, s), d_res(ctx, s), d_codes(ctx, s), d_words(ctx, s),
+        d_state(ctx, s), d_lens(ctx, s), d_dst(ctx, s), d_packed(ctx, s);
+    const auto min16 = [](size_t n) { return std::max<size_t>(n, 16); };
+    HIP_TRY(upload_seqs(dq, dd, q_seq, q_off, n_q, db_seq, db_off, n_db, 16));
+    HIP_TRY(d_pairs.alloc(min16(max_n * sizeof(EfPair))));
+    HIP_TRY(d_res.alloc(min16(n_pairs * sizeof(saln_ends_free_result))));
+    if (!chunks.empty()) {
+        HIP_TRY(d_codes.alloc(min16(max_bytes)));
+        HIP_TRY(d_words.alloc(min16(max_words * sizeof(uint32_t))));
+        HIP_TRY(d_packed.alloc(min16(max_words * sizeof(uint32_t))));
+        HIP_TRY(d_state.alloc(min16(n_pairs)));
+        HIP_TRY(d_lens.alloc(min16(max_n * sizeof(uint32_t))));
+        HIP_TRY(d_dst.alloc(min16(max_n * sizeof(uint64_t))));
+    }
+    const uint8_t *sq = dq.as<uint8_t>(), *sd = dd.as<uint8_t>();
+    auto *results = d_res.as<saln_ends_free_result>();
+    std::vector<Launch> launches;
+
+    if (!plain.pairs.empty()) {
+        plan_launches(&plain.pairs, &launches);
+        HIP_TRY(hipMemcpyAsync(d_pairs.p, plain.pairs.data(), plain.pairs.size() * sizeof(EfPair),
+                               hipMemcpyHostToDevice, s));
+        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s);
+        if (rc != SALN_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(s));  // d_pairs and the host vector are reused
+    }
+    // Per chunk: the fills with codes and the walk (each pair's words at the
+    // end of its own area), the word counts back, then the words packed on
+    // the device in pair order and copied to the end of the handle's words:
+    // chunks hold rising pair indices, so the handle's words stay in pair order.
+    constexpr uint64_t kNoWords = ~0ull;
+    std::fill(aln->off.begin(), aln->off.end(), kNoWords);
+    std::vector<uint32_t> lens, order;
+    std::vector<uint64_t> dst;
+    for (Chunk &c : chunks) {
+        const uint32_t n = (uint32_t)c.pairs.size();
+        // the fills and the walk read the same descriptors, in the fills' order
+        plan_launches(&c.pairs, &launches);
+        HIP_TRY(hipMemcpyAsync(d_pairs.p, c.pairs.data(), n * sizeof(EfPair), hipMemcpyHostToDevice, s));
+        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
+                       d_state.as<uint8_t>(), results, s);
+        if (rc != SALN_OK) return rc;
+        HIP_TRY(launch_ef_walk(local, d_pairs.as<EfPair>(), n, sq, sd, d_codes.as<uint8_t>(),
+                               d_state.as<uint8_t>(), results, d_words.as<uint32_t>(),
+                               d_lens.as<uint32_t>(), s));
+        lens.resize(n);
+        HIP_TRY(hipMemcpyAsync(lens.data(), d_lens.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        order.resize(n);
+        for (uint32_t i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(),
+                  [&](uint32_t x, uint32_t y) { return c.pairs[x].out < c.pairs[y].out; });
+        dst.resize(n);
+        const uint64_t base = aln->words.size();
+        uint64_t total = 0;
+        for (const uint32_t i : order) {
+            const EfPair &p = c.pairs[i];
+            lens[i] = std::min(lens[i], p.lq + p.ld);
+            dst[i] = total;
+            aln->off[p.out] = base + total;
+            total += lens[i];
+        }
+        if (total) {
+            HIP_TRY(hipMemcpyAsync(d_dst.p, dst.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            HIP_TRY(launch_ef_gather(d_pairs.as<EfPair>(), n, d_words.as<uint32_t>(),
+                                     d_lens.as<uint32_t>(), d_dst.as<uint64_t>(),
+                                     d_packed.as<uint32_t>(), s));
+            aln->words.resize(base + total);
+            HIP_TRY(hipMemcpyAsync(aln->words.data() + base, d_packed.p, total * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        std::vector<EfPair>().swap(c.pairs);
+    }
+    HIP_TRY(hipMemcpy(aln->res.data(), d_res.p, n_pairs * sizeof(saln_ends_free_result),
+                      hipMemcpyDeviceToHost));
+    // pairs without words sit where the next pair's words begin
+    uint64_t cur = 0;
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        saln_ends_free_result &r = aln->res[k];
+        if (capped[k]) r.status = SALN_TRACE_CAP;
+        if (aln->off[k] == kNoWords) {
+            aln->off[k] = cur;
+            r.cigar_len = 0;
+        } else {
+            r.cigar_len = (uint32_t)std::min<uint64_t>(r.cigar_len, aln->words.size() - aln->off[k]);
+            cur = aln->off[k] + r.cigar_len;
+        }
+    }
+    aln->off[n_pairs] = aln->words.size();
+    *out = aln.release();
+    return SALN_OK;
+}
+
+uint64_t saln_ends_free_aln_count(const saln_ends_free_aln *a) { return a ? a->res.size() : 0; }
+
+int saln_ends_free_aln_get(const saln_ends_free_aln *a, uint64_t pair, saln_ends_free_result *res,
+                           const uint32_t **cigar) {
+    if (!a || pair >= a->res.size()) return SALN_E_INVALID;
+    if (res) *res = a->res[pair];
+    if (cigar) *cigar = a->words.data() + a->off[pair];
+    return SALN_OK;
+}
+
+void saln_ends_free_aln_free(saln_ends_free_aln *a) { delete a; }
+
+}  // extern "C"
