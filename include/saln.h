@@ -743,7 +743,9 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  * Limits: a query of at most 1,024 columns (one chunk of the lane fill;
  * saln_ends_free_pair_geometry reports its class) and a db of at most 65,000
  * rows (a group's db row is staged in LDS); a longer sequence makes the batch
- * SALN_E_INVALID with a message naming the limit. */
+ * SALN_E_INVALID with a message naming the limit.  Longer pairs:
+ * saln_ends_free_long_align_batch, below, whose only limit is the range
+ * guard. */
 typedef struct {
     int32_t score, status;            /* SALN_OK | SALN_TRACE_CAP */
     int32_t q_begin, q_end, db_begin, db_end;   /* begins -1 when no walk ran */
@@ -799,6 +801,47 @@ int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes)
  * 64 x 8, 64 x 16: the smallest that holds the query).  SALN_E_INVALID above
  * 1,024 columns.  The launch code asks the same function. */
 int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols_per_lane);
+
+/* Pairs of any length (ends_free_long_kernels.hip, ends_free_long_host.cpp).
+ * saln_ends_free_long_align_batch is saln_ends_free_align_batch without the
+ * two length limits: the same arguments, modes, scoring domain, range guard,
+ * pair conventions, want_cigar, trace_budget_bytes chunking, SALN_TRACE_CAP
+ * meaning and handle (saln_ends_free_aln_count / _get / _free serve it).  The
+ * only limit left is the range guard, (n + m + 2) * max|parameter| < 2^30.
+ * A pair within the limits above (n <= 1,024 and m <= 65,000) runs the class
+ * fills; every other pair runs the chunked fill: one pair per wave, the query
+ * in chunks of 1,024 columns left to right, every db row in each chunk, the
+ * last column of a chunk handed to the next through a boundary column in
+ * device memory, the db read as the rows come.  The definitions above
+ * (recurrences, tie rules, the walk's choices) are unchanged, so a pair's
+ * record and words depend on nothing but the pair and the scoring, whichever
+ * fill ran it.  A pair's codes are saln_ends_free_long_trace_bytes.
+ * Boundary workspace: 8 * m bytes per pair in flight.  Every wave of a
+ * chunked-fill launch owns one slot of 8 bytes per row of the launch's
+ * longest db and takes pairs from a counter; a launch runs min(pairs, 4,096,
+ * 256 MiB / slot bytes) waves and at least one, so the workspace stays within
+ * 256 MiB however large the batch; a single db above 33,554,432 rows runs
+ * alone in a slot of its own size. */
+int saln_ends_free_long_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                    uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                    uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                    uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                                    uint64_t trace_budget_bytes, int want_cigar,
+                                    saln_ends_free_aln **out);
+/* Host only: bytes of trace codes of one pair under the long entry point, the
+ * one place the long layout's size is computed (the batch's chunking asks
+ * it).  A pair within the class limits: saln_ends_free_trace_bytes.  Every
+ * other pair: len_db rows of ceil(len_q / 16) * 8 bytes, rounded up to a
+ * multiple of 8; 0 when a sequence is empty.  SALN_E_INVALID as
+ * saln_ends_free_long_pair_path. */
+int saln_ends_free_long_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes);
+/* Host only: the fill a pair takes under the long entry point; the launch
+ * code asks the same function.  *long_fill: 1 the chunked fill, 0 a class
+ * fill (saln_ends_free_pair_geometry tells which).  *chunks: the pair's
+ * 1,024-column chunks; 1 for the class fills.  SALN_E_INVALID only where the
+ * range guard cannot hold for any scoring: len_q + len_db + 2 >= 2^30. */
+int saln_ends_free_long_pair_path(uint64_t len_q, uint64_t len_db, int32_t *long_fill,
+                                  uint32_t *chunks);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

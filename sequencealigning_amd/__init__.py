@@ -16,7 +16,8 @@ from .wfa import WfaAlignment, WfaPlan, wfa_align, wfa_align_batch
 from . import wfa_affine
 from .wfa_affine import wfa_affine_align, wfa_affine_align_batch
 from . import ends_free
-from .ends_free import EndsFreePlan, ends_free_align_batch, local_align, semi_global_align
+from .ends_free import (EndsFreePlan, ends_free_align_batch, ends_free_align_long_batch, local_align,
+                        local_align_long, semi_global_align, semi_global_align_long)
 from ._lib import get_option, option_names, options, set_option
 
 __all__ = [
@@ -26,5 +27,6 @@ __all__ = [
     "wfa", "WfaAlignment", "WfaPlan", "wfa_align", "wfa_align_batch", "wfa_affine",
     "wfa_affine_align", "wfa_affine_align_batch",
     "ends_free", "EndsFreePlan", "ends_free_align_batch", "local_align", "semi_global_align",
+    "ends_free_align_long_batch", "local_align_long", "semi_global_align_long",
     "get_option", "option_names", "options", "set_option",
 ]

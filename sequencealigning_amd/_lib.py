@@ -142,6 +142,8 @@ EXPORTS = [
     "saln_ends_free_align_batch", "saln_ends_free_aln_count", "saln_ends_free_aln_get",
     "saln_ends_free_aln_free", "saln_ends_free_plan_create", "saln_ends_free_execute",
     "saln_ends_free_plan_destroy", "saln_ends_free_trace_bytes", "saln_ends_free_pair_geometry",
+    "saln_ends_free_long_align_batch", "saln_ends_free_long_trace_bytes",
+    "saln_ends_free_long_pair_path",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -303,6 +305,10 @@ def lib() -> C.CDLL:
         L.saln_ends_free_plan_destroy.argtypes = [vp]
         L.saln_ends_free_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
         L.saln_ends_free_pair_geometry.argtypes = [C.c_uint64, u32p, u32p]
+        L.saln_ends_free_long_align_batch.argtypes = L.saln_ends_free_align_batch.argtypes
+        L.saln_ends_free_long_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
+        L.saln_ends_free_long_pair_path.argtypes = [C.c_uint64, C.c_uint64,
+                                                    C.POINTER(C.c_int32), u32p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "saln.h"
@@ -51,6 +52,41 @@ inline uint32_t ef_row_bytes(uint64_t len_q) {
     return (uint32_t)((len_q + k - 1) / k * (k / 2));
 }
 
+// The chunked fill (ends_free_long_kernels.hip, saln_ends_free_long_*): the
+// 64 x 16 class run over chunks of kEfChunkCols query columns, the db read as
+// it goes.  It takes the pairs the classes refuse.
+constexpr int kEfLongClass = kEfClasses;
+constexpr uint64_t kEfChunkCols = 1024;
+static_assert(kEfChunkCols == kEfMaxQ, "a chunk is the widest class");
+
+// The fill a pair runs in: its class, kEfLongClass, or -1 (refused).  long_ok:
+// the caller is a saln_ends_free_long_* entry point.  The one place the
+// decision is made: saln_ends_free_long_pair_path, the code sizes and the
+// launches all ask it.
+inline int ef_path_of(uint64_t len_q, uint64_t len_db, bool long_ok) {
+    if (len_q <= kEfMaxQ && len_db <= kEfMaxDb) return ef_class_of(len_q);
+    return long_ok ? kEfLongClass : -1;
+}
+
+// Bytes of one code row under the chunked fill: 8 per lane that holds a column.
+inline uint64_t ef_long_row_bytes(uint64_t len_q) { return (len_q + 15) / 16 * 8; }
+inline uint64_t ef_path_row_bytes(int path, uint64_t len_q) {
+    return path == kEfLongClass ? ef_long_row_bytes(len_q) : ef_row_bytes(len_q);
+}
+
+// Boundary workspace of the chunked fill.  Every wave of a launch owns one
+// slot, a column of 8 bytes per row of the launch's longest db, and takes
+// pairs from a counter; a launch runs min(pairs, kEfLongWaves,
+// kEfLongWorkspace / slot bytes) waves and at least one, so the workspace
+// stays within kEfLongWorkspace however large the batch is, except for a
+// single db whose column alone exceeds it.
+constexpr uint64_t kEfLongWorkspace = 256ull << 20;
+constexpr uint32_t kEfLongWaves = 4096;
+inline uint32_t ef_long_slots(uint64_t count, uint64_t ld_max) {
+    const uint64_t fit = kEfLongWorkspace / (8 * (ld_max ? ld_max : 1));
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({count, kEfLongWaves, fit}));
+}
+
 // Dynamic LDS of a fill workgroup of `groups` lane groups: each group's db
 // row, padded by `lanes` bytes on both sides (the skew reads past the ends).
 inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
@@ -64,6 +100,13 @@ hipError_t launch_ef_fill(int cls, bool local, const EfPair *pairs, uint32_t fir
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
                           uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
                           hipStream_t s);
+// Chunked fill of pairs[first .. first + count) (any lengths): `slots` waves,
+// each with slot_rows (>= the longest db) 8-byte entries of bnd, taking pairs
+// from *counter, which the caller has zeroed on the stream.
+hipError_t launch_ef_fill_long(bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
+                               uint8_t *end_state, saln_ends_free_result *results, void *bnd,
+                               uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s);
 // Walk of pairs[0 .. count): one pair per lane, from the end cell the fill
 // reported.  A pair's words end at words[cig_off + lq + ld), cigar_len of
 // them (also in lens, indexed like pairs).

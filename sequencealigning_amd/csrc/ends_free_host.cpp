@@ -10,6 +10,11 @@
 // most trace_budget_bytes of codes; per chunk the fill with codes, the walk,
 // the words packed on the device in pair order, then the words back.  Pairs
 // whose codes alone exceed the budget run in a score-only fill of their own.
+//
+// The batch (ef_align_batch) also serves saln_ends_free_long_align_batch
+// (ends_free_long_host.cpp): with long_ok the pairs above this file's length
+// limits are not refused but run the chunked fill, one more class to
+// plan_launches; everything else is shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,8 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "ends_free.hpp"
-#include "host_common.hpp"
+#include "ends_free_host.hpp"
 
 using namespace saln;
 
@@ -36,16 +40,16 @@ int bit_bucket(uint32_t v) {
 }
 
 // Orders pairs for the fill (class, then falling db length) and cuts them
-// into launches.
-void plan_launches(std::vector<EfPair> *pairs, std::vector<Launch> *out) {
-    std::stable_sort(pairs->begin(), pairs->end(), [](const EfPair &a, const EfPair &b) {
-        const int ca = ef_class_of(a.lq), cb = ef_class_of(b.lq);
+// into launches.  long_ok: the chunked fill is one more class (ef_path_of).
+void plan_launches(std::vector<EfPair> *pairs, std::vector<Launch> *out, bool long_ok = false) {
+    std::stable_sort(pairs->begin(), pairs->end(), [long_ok](const EfPair &a, const EfPair &b) {
+        const int ca = ef_path_of(a.lq, a.ld, long_ok), cb = ef_path_of(b.lq, b.ld, long_ok);
         return ca != cb ? ca < cb : a.ld > b.ld;
     });
     out->clear();
     for (uint32_t k = 0; k < pairs->size(); ++k) {
         const EfPair &p = (*pairs)[k];
-        const int cls = ef_class_of(p.lq);
+        const int cls = ef_path_of(p.lq, p.ld, long_ok);
         if (out->empty() || out->back().cls != cls ||
             bit_bucket(out->back().ld_max) != bit_bucket(p.ld))
             out->push_back(Launch{cls, k, 0, p.ld});
@@ -80,15 +84,18 @@ int make_scoring(const saln_nw_scoring *s, EfScoring *out, uint64_t *max_abs) {
 }
 
 // The engine's limits for one pair (lengths, int32 range of the values).
-int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs) {
-    if (lq > kEfMaxQ) {
+// long_ok: the chunked fill takes the lengths the classes refuse.
+int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs, bool long_ok = false) {
+    if (lq > kEfMaxQ && !long_ok) {
         set_error("ends_free: a query of " + std::to_string(lq) + " columns is above the limit of " +
-                  std::to_string(kEfMaxQ) + " (one chunk of the lane fill)");
+                  std::to_string(kEfMaxQ) + " (one chunk of the lane fill); "
+                  "saln_ends_free_long_align_batch takes longer pairs");
         return SALN_E_INVALID;
     }
-    if (ld > kEfMaxDb) {
+    if (ld > kEfMaxDb && !long_ok) {
         set_error("ends_free: a db of " + std::to_string(ld) + " rows is above the limit of " +
-                  std::to_string(kEfMaxDb) + " (the db row is staged in LDS)");
+                  std::to_string(kEfMaxDb) + " (the db row is staged in LDS); "
+                  "saln_ends_free_long_align_batch takes longer pairs");
         return SALN_E_INVALID;
     }
     if ((lq + ld + 2) * max_abs >= (1ull << 30)) {
@@ -104,16 +111,23 @@ uint64_t code_bytes(uint64_t lq, uint64_t ld) {
     return (ld * ef_row_bytes(lq) + 7) & ~7ull;
 }
 
+// The same under the long entry points, which own the long layout's size.
+uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok) {
+    uint64_t bytes = 0;
+    if (!long_ok) return code_bytes(lq, ld);
+    return saln_ends_free_long_trace_bytes(lq, ld, &bytes) == SALN_OK ? bytes : 0;
+}
+
 int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
                 const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, uint64_t max_abs,
-                std::vector<EfPair> *out) {
+                std::vector<EfPair> *out, bool long_ok = false) {
     out->resize(n_pairs);
     const PairIndex pairs{pair_q, pair_db, n_q, n_db};
     for (uint64_t k = 0; k < n_pairs; ++k) {
         uint64_t qi, di;
         if (!pairs.at(k, &qi, &di)) return SALN_E_INVALID;
         const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        const int rc = check_pair(lq, ld, max_abs);
+        const int rc = check_pair(lq, ld, max_abs, long_ok);
         if (rc != SALN_OK) return rc;
         EfPair p{};
         p.q_off = q_off[qi];
@@ -121,19 +135,29 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
         p.lq = (uint32_t)lq;
         p.ld = (uint32_t)ld;
         p.out = (uint32_t)k;
-        p.row_bytes = ef_row_bytes(lq);
+        p.row_bytes = (uint32_t)ef_path_row_bytes(ef_path_of(lq, ld, long_ok), lq);
         (*out)[k] = p;
     }
     return SALN_OK;
 }
 
-// The fills of `pairs` (device copy d_pairs, in plan_launches' order).
+// The fills of `pairs` (device copy d_pairs, in plan_launches' order).  ws:
+// the chunked fill's workspace (launches of kEfLongClass need one).
 int run_fills(const std::vector<Launch> &launches, bool local, const EfPair *d_pairs,
               const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, uint8_t *d_codes,
-              uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s) {
-    for (const Launch &l : launches)
+              uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
+              EfLongWorkspace *ws = nullptr) {
+    for (const Launch &l : launches) {
+        if (l.cls == kEfLongClass) {
+            if (!ws) return SALN_E_INVALID;
+            const int rc = ef_long_fill(ws, local, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+                                        d_codes, d_end_state, d_results, s);
+            if (rc != SALN_OK) return rc;
+            continue;
+        }
         HIP_TRY(launch_ef_fill(l.cls, local, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
                                d_codes, d_end_state, d_results, s));
+    }
     return SALN_OK;
 }
 
@@ -218,12 +242,16 @@ int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
     return SALN_OK;
 }
 
-int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
-                               uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
-                               uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
-                               uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
-                               uint64_t trace_budget_bytes, int want_cigar,
-                               saln_ends_free_aln **out) {
+}  // extern "C"
+
+// saln_ends_free_align_batch (long_ok = false) and
+// saln_ends_free_long_align_batch (true): the same batch, with or without the
+// chunked fill for the pairs the classes refuse.
+int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
+                         const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
+                         const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
+                         int32_t mode, const saln_nw_scoring *scoring, uint64_t trace_budget_bytes,
+                         int want_cigar, saln_ends_free_aln **out, bool long_ok) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     EfScoring sc{};
@@ -232,7 +260,7 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
     if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs);
     std::vector<EfPair> all;
     if (rc == SALN_OK)
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all);
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all, long_ok);
     if (rc != SALN_OK) return rc;
     const bool local = mode == SALN_MODE_LOCAL;
     auto aln = std::make_unique<saln_ends_free_aln>();
@@ -255,7 +283,7 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
     std::vector<uint8_t> capped(n_pairs, 0);
     for (uint64_t k = 0; k < n_pairs; ++k) {
         EfPair p = all[k];
-        const uint64_t bytes = code_bytes(p.lq, p.ld);
+        const uint64_t bytes = code_bytes(p.lq, p.ld, long_ok);
         if (!want_cigar || bytes > budget) {
             capped[k] = want_cigar ? 1 : 0;
             plain.pairs.push_back(p);
@@ -298,12 +326,14 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
     const uint8_t *sq = dq.as<uint8_t>(), *sd = dd.as<uint8_t>();
     auto *results = d_res.as<saln_ends_free_result>();
     std::vector<Launch> launches;
+    EfLongWorkspace ws(ctx, s);
 
     if (!plain.pairs.empty()) {
-        plan_launches(&plain.pairs, &launches);
+        plan_launches(&plain.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, plain.pairs.data(), plain.pairs.size() * sizeof(EfPair),
                                hipMemcpyHostToDevice, s));
-        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s);
+        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s,
+                       &ws);
         if (rc != SALN_OK) return rc;
         HIP_TRY(hipStreamSynchronize(s));  // d_pairs and the host vector are reused
     }
@@ -318,10 +348,10 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
     for (Chunk &c : chunks) {
         const uint32_t n = (uint32_t)c.pairs.size();
         // the fills and the walk read the same descriptors, in the fills' order
-        plan_launches(&c.pairs, &launches);
+        plan_launches(&c.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, c.pairs.data(), n * sizeof(EfPair), hipMemcpyHostToDevice, s));
         rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
-                       d_state.as<uint8_t>(), results, s);
+                       d_state.as<uint8_t>(), results, s, &ws);
         if (rc != SALN_OK) return rc;
         HIP_TRY(launch_ef_walk(local, d_pairs.as<EfPair>(), n, sq, sd, d_codes.as<uint8_t>(),
                                d_state.as<uint8_t>(), results, d_words.as<uint32_t>(),
@@ -373,6 +403,18 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
     aln->off[n_pairs] = aln->words.size();
     *out = aln.release();
     return SALN_OK;
+}
+
+extern "C" {
+
+int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                               uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                               uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                               uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                               uint64_t trace_budget_bytes, int want_cigar,
+                               saln_ends_free_aln **out) {
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                          scoring, trace_budget_bytes, want_cigar, out, false);
 }
 
 uint64_t saln_ends_free_aln_count(const saln_ends_free_aln *a) { return a ? a->res.size() : 0; }

@@ -1,0 +1,262 @@
+// The chunked fill of the ends-free engine (include/saln.h,
+// saln_ends_free_long_*): pairs whose query is longer than one chunk of the
+// 64 x 16 lane fill, or whose db is too long to stage in LDS.  DESIGN.md
+// section 3d.  The walk and the gather are those of ends_free_kernels.hip:
+// the codes keep the layout of ends_free_dev.hpp.
+//
+// ef_fill_long_kernel is the 64 x 16 decomposition of ef_fill_kernel (one
+// pair per wave, 16 columns per lane in registers, rows skewed over the
+// lanes, wave_shr:1 hand-over, plain int32).  What differs:
+//  - the wave walks the query in chunks of 1,024 columns, left to right, and
+//    runs every db row in each.  Lane 63 publishes (P(r, c0), I(r, c0 + 1))
+//    of the next chunk's first column c0 into the wave's boundary column in
+//    HBM; lane 0 of the next chunk takes them where chunk 0 takes constants.
+//    The same wave writes and reads the column, a chunk apart: nothing waits
+//    on another wave;
+//  - the db is not staged whole: a 128-byte LDS ring holds the rows that are
+//    live in the skew (t - 63 .. t at step t), refilled every 64 steps from a
+//    register loaded 64 steps ahead;
+//  - local's best cell: a best per chunk on strict > (rows rise inside a
+//    chunk), merged into the running best on (value, row) at the chunk's end,
+//    and a final reduction over the lanes on (value, row, column) in full
+//    32-bit words.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "ends_free_dev.hpp"
+
+namespace saln {
+
+namespace {
+constexpr int kLanes = 64, kCols = 16;  // the 64 x 16 class
+constexpr uint32_t kRing = 128;         // db bytes of two refills
+static_assert(kLanes * kCols == (int)kEfChunkCols, "a chunk is one 64 x 16 fill");
+}  // namespace
+
+// One wave per workgroup; workgroup w owns boundary slot w (slot_rows entries
+// of bnd) and takes pairs from *counter until none is left.
+//
+// bnd is read and written in this kernel, so it is neither const nor
+// __restrict__: its loads must stay ordinary vector loads behind the fence,
+// not scalar or invariant ones.  One column per slot, updated in place: entry
+// r - 1 (row r) is read by lane 0 before step r - 1 (the refill that loads it
+// runs at most 128 steps earlier) and written by lane 63 at step r + 62, both
+// by this wave in program order, so a row's old value is always consumed
+// before its new one is stored.
+template <bool kLocal, bool kCodes>
+__global__ __launch_bounds__(64) void ef_fill_long_kernel(
+    const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
+    const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
+    uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
+    int2 *bnd, uint64_t slot_rows, uint32_t *counter) {
+    constexpr int K = kCols;
+    __shared__ uint8_t ring[kRing];
+    const int lane = (int)threadIdx.x;
+    int2 *col = bnd + (size_t)blockIdx.x * slot_rows;
+    const int32_t o = sc.open, e = sc.extend;
+    for (;;) {
+        uint32_t gi = 0;
+        if (lane == 0) gi = atomicAdd(counter, 1u);
+        gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)gi);
+        if (gi >= count) return;
+        const EfPair p = pairs[first + gi];
+        const uint32_t lq = p.lq, ld = p.ld;
+        const uint8_t *__restrict__ q = qs + p.q_off;
+        const uint8_t *__restrict__ d = ds + p.d_off;
+        saln_ends_free_result res;
+        res.status = SALN_OK;
+        res.q_begin = res.db_begin = -1;
+        res.cigar_len = res.reserved = 0;
+        if (lq == 0) {  // no column: score 0 at the origin in both modes
+            if (lane == 0) {
+                res.score = res.q_end = res.db_end = 0;
+                results[p.out] = res;
+                if constexpr (kCodes) end_state[p.out] = 0;
+            }
+            continue;
+        }
+        const uint32_t nchunks = (lq + kEfChunkCols - 1) / (uint32_t)kEfChunkCols;
+        const uint32_t jend = lq - 1;
+        // the lane and register of column lq in the last chunk
+        const uint32_t l_end = jend % (uint32_t)kEfChunkCols / K, k_end = jend % K;
+        // running best.  local: best_j is the absolute column.  semi-global:
+        // the single owner restarts from row 0 in every chunk, the last counts
+        int32_t best = kLocal ? 0 : o + (int32_t)lq * e;
+        uint32_t best_i = 0, best_j = 0, best_st = kLocal ? 0u : 1u;  // row 0 ends in I
+        const int T = ld ? (int)ld + kLanes - 1 : 0;  // no row: the row-0 values stand
+        for (uint32_t c = 0; c < nchunks; ++c) {
+            const uint32_t col0 = c * (uint32_t)kEfChunkCols + (uint32_t)lane * K;  // my columns: col0+1 .. col0+K
+            const bool publish = lane == kLanes - 1 && c + 1 < nchunks;
+            uint32_t qc[K];
+            int32_t Hp[K], Dn[K];  // P(r-1, j) and D(r, j) of my columns
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const uint32_t j = col0 + k + 1;
+                qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
+                Hp[k] = kLocal ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
+                Dn[k] = kEfNeg;
+            }
+            // P(0, col0), by the absolute column: also lane 0 of a chunk c > 0
+            int32_t hd = kLocal || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
+            int32_t pubF = kEfNeg, pubH = kEfNeg;
+            // this chunk's best of my columns, as ef_fill_kernel keeps it: rows
+            // rise inside a chunk, so strict > keeps the smallest row, then
+            // the smallest column.  (Local pad columns need no mask: a pad
+            // cell's M lies strictly below some real M of the pair, so it can
+            // only displace a lane's value that is not the pair's best.)
+            int32_t cbest = kLocal ? 0 : o + (int32_t)lq * e;
+            uint32_t cbest_i = 0, cbest_k = kLocal ? 0u : 1u;  // semi-global: cbest_k is the end state
+            uint8_t *crow = nullptr;
+            if constexpr (kCodes) crow = codes + p.code_off + (size_t)c * (kEfChunkCols / 2) + (size_t)lane * (K / 2);
+            // rows t + 64 .. t + 127 of the db and of the boundary column,
+            // loaded at the refill of step t and used from step t + 64 on.
+            // Rows past the db are never used: their loads repeat the last row
+            uint32_t dnext = 0;
+            int2 bnext = make_int2(0, 0), bcur = make_int2(0, 0);
+            if (T) dnext = d[min((uint32_t)lane, ld - 1)];
+            if (T && c > 0) {
+                // lane 63's stores of chunk c - 1 before lane 0's loads
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                bnext = col[min((uint32_t)lane, ld - 1)];
+            }
+            // the query bytes have arrived: inside the loop only the refill waits for loads
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+            for (int t0 = 0; t0 < T; t0 += kLanes) {
+                // the refill.  One wave: its LDS accesses execute in program order
+                ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)dnext;
+                bcur = bnext;
+                const uint32_t inext = min((uint32_t)t0 + kLanes + (uint32_t)lane, ld - 1);
+                dnext = d[inext];
+                if (c > 0) bnext = col[inext];
+                __builtin_amdgcn_wave_barrier();
+                const int tend = min(t0 + kLanes, T);
+                for (int t = t0; t < tend; ++t) {
+                    const int s = t - t0;
+                    const int r = t - lane + 1;
+                    const uint32_t dch = ring[(uint32_t)(t - lane) & (kRing - 1)];  // d[r-1]
+                    // column c0 entering lane 0.  Chunk 0: P(i, 0) = 0 in both
+                    // modes, I(i, 1) opens from M(i, 0) = 0 in semi-global and is
+                    // -inf in local.  Later chunks: what lane 63 published for row t + 1
+                    int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
+                    if (c > 0) {
+                        bH = __builtin_amdgcn_readlane(bcur.x, s);
+                        bF = __builtin_amdgcn_readlane(bcur.y, s);
+                    }
+                    const int32_t inF = ef_shr1<kLanes>(bF, pubF);  // I(r, col0+1)
+                    const int32_t inH = ef_shr1<kLanes>(bH, pubH);  // P(r, col0)
+                    if (r >= 1 && r <= (int)ld) {
+                        int32_t F = inF;
+                        int32_t Msel = kEfNeg, Isel = kEfNeg;
+                        uint32_t nlo = 0, nhi = 0;
+#pragma unroll
+                        for (int k = 0; k < K; ++k) {
+                            const int32_t M = ef_add(hd, qc[k] == dch ? sc.match : sc.mismatch);
+                            const int32_t I = F, D = Dn[k];
+                            const int32_t P3 = max(M, max(I, D));
+                            const int32_t P = kLocal ? max(P3, 0) : P3;
+                            const int32_t tO = ef_add(M, o);
+                            if constexpr (kCodes) {
+                                uint32_t cd = M == P3 ? 0u : I == P3 ? 1u : 2u;
+                                if constexpr (kLocal) cd = P3 <= 0 ? kEfStop : cd;
+                                cd |= I >= tO ? kEfIExt : 0u;
+                                cd |= D >= tO ? kEfDExt : 0u;
+                                if (k < 8)
+                                    nlo |= cd << (4 * k);
+                                else
+                                    nhi |= cd << (4 * (k - 8));
+                            }
+                            if constexpr (kLocal) {
+                                const bool b = M > cbest;
+                                cbest = b ? M : cbest;
+                                cbest_i = b ? (uint32_t)r : cbest_i;
+                                cbest_k = b ? (uint32_t)k : cbest_k;
+                            } else {
+                                Msel = (uint32_t)k == k_end ? M : Msel;
+                                Isel = (uint32_t)k == k_end ? I : Isel;
+                            }
+                            F = ef_add(max(tO, I), e);      // I(r, j+1)
+                            Dn[k] = ef_add(max(tO, D), e);  // D(r+1, j)
+                            hd = Hp[k];
+                            Hp[k] = P;
+                        }
+                        hd = inH;
+                        pubF = F;
+                        pubH = Hp[K - 1];
+                        if (publish) col[r - 1] = make_int2(pubH, pubF);
+                        if constexpr (!kLocal) {
+                            const int32_t v = max(Msel, Isel);
+                            const bool b = v > cbest;  // the smallest row wins a tie
+                            cbest = b ? v : cbest;
+                            cbest_i = b ? (uint32_t)r : cbest_i;
+                            cbest_k = b ? (Msel >= Isel ? 0u : 1u) : cbest_k;  // M before I
+                        }
+                        if constexpr (kCodes) {
+                            if (col0 < lq)  // lanes wholly past the query store nothing
+                                *reinterpret_cast<uint2 *>(crow + (size_t)(r - 1) * p.row_bytes) = make_uint2(nlo, nhi);
+                        }
+                    }
+                }
+            }
+            if constexpr (kLocal) {
+                // a later chunk holds larger columns but starts over at row 1:
+                // it wins with a larger value, or the same value in a smaller row
+                const bool take = cbest > best || (cbest == best && cbest > 0 && cbest_i < best_i);
+                best = take ? cbest : best;
+                best_i = take ? cbest_i : best_i;
+                best_j = take ? col0 + cbest_k + 1 : best_j;
+            } else {
+                best = cbest;
+                best_i = cbest_i;
+                best_st = cbest_k;
+            }
+        }
+        if constexpr (kLocal) {
+            // the wave's best: the largest value, then the smallest row, then
+            // the smallest column.  Lanes without a positive cell lose.
+            uint32_t bi = best > 0 ? best_i : 0xFFFFFFFFu, bj = best_j;
+#pragma unroll
+            for (int off = kLanes / 2; off >= 1; off >>= 1) {
+                const int32_t ov = __shfl_xor(best, off, kLanes);
+                const uint32_t oi = __shfl_xor(bi, off, kLanes);
+                const uint32_t oj = __shfl_xor(bj, off, kLanes);
+                const bool take = ov > best || (ov == best && (oi < bi || (oi == bi && oj < bj)));
+                best = take ? ov : best;
+                bi = take ? oi : bi;
+                bj = take ? oj : bj;
+            }
+            if (lane == 0) {
+                res.score = best;
+                res.db_end = best > 0 ? (int32_t)bi : 0;
+                res.q_end = best > 0 ? (int32_t)bj : 0;
+                results[p.out] = res;
+                if constexpr (kCodes) end_state[p.out] = 0;
+            }
+        } else if ((uint32_t)lane == l_end) {
+            res.score = best;
+            res.db_end = (int32_t)best_i;
+            res.q_end = (int32_t)lq;
+            results[p.out] = res;
+            if constexpr (kCodes) end_state[p.out] = (uint8_t)best_st;
+        }
+        // the next pair reuses the boundary column and the ring
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    }
+}
+
+hipError_t launch_ef_fill_long(bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
+                               uint8_t *end_state, saln_ends_free_result *results, void *bnd,
+                               uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    if (slots == 0 || !bnd || !counter) return hipErrorInvalidValue;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(slots), dim3(kLanes), 0, s, pairs, first, count, qs, ds, codes,
+                           end_state, results, sc, static_cast<int2 *>(bnd), slot_rows, counter);
+        return hipGetLastError();
+    };
+    if (local) return codes ? go(ef_fill_long_kernel<true, true>) : go(ef_fill_long_kernel<true, false>);
+    return codes ? go(ef_fill_long_kernel<false, true>) : go(ef_fill_long_kernel<false, false>);
+}
+
+}  // namespace saln

@@ -16,6 +16,13 @@ against a db base; the db is the reference sequence).
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
 include/saln.h and DESIGN.md; the checker is tests/ends_free_model.py.
+
+``ends_free_align_batch`` and its one-pair forms take a query of at most
+1,024 columns and a db of at most 65,000 rows.  ``ends_free_align_long_batch``,
+``local_align_long`` and ``semi_global_align_long`` take pairs of any length
+within the range guard ((n + m + 2) * max|parameter| < 2^30): a pair above the
+limits runs the chunked fill (ends_free_long_kernels.hip), every other pair
+the same fills as before, with the same records and words.
 """
 from __future__ import annotations
 
@@ -45,26 +52,18 @@ def _pair_lists(pairs, n_q, n_db):
     return np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1]), len(pairs)
 
 
-def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace_budget: int = 0,
-                          cigar: bool = True, device: int = 0):
-    """Local or semi-global alignment of a batch.  pairs: None (all-vs-all, db
-    outer / query inner) or (n, 2) (query index, db index).  Returns (results,
-    cigars): results is a structured array (score, status, q_begin, q_end,
-    db_begin, db_end, cigar_len; the ranges half-open and 0-based), cigars a
-    CigarBatch (pair k's [(length, op), ...]).  cigar=False runs the fill only:
-    score and ends, begins -1, no words.  A pair whose trace codes alone exceed
-    trace_budget bytes (0 selects 1 GiB per chunk) has status TRACE_CAP, its
-    score and ends, begins -1 and no words."""
+def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar, device):
+    """saln_ends_free_align_batch or saln_ends_free_long_align_batch (entry)."""
     qs, qo = pack_csr(queries)
     ds, do = pack_csr(dbs)
     pq, pd, n = _pair_lists(pairs, len(qo) - 1, len(do) - 1)
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
     L = _lib.lib()
     h = C.c_void_p()
-    _lib.check(L.saln_ends_free_align_batch(
+    _lib.check(getattr(L, entry)(
         _lib.context(device), vp(qs), vp(qo), len(qo) - 1, vp(ds), vp(do), len(do) - 1, vp(pq),
         vp(pd), n, _mode(mode), _lib.scoring_arg(scoring), int(trace_budget), int(bool(cigar)),
-        C.byref(h)), "saln_ends_free_align_batch")
+        C.byref(h)), entry)
     try:
         res = np.zeros(n, dtype=_lib.ENDS_FREE_RESULT_DTYPE)
         r = _lib.EndsFreeResult()
@@ -87,9 +86,34 @@ def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace
     return res, CigarBatch(words, offs, lens)
 
 
-def _one(seq1, seq2, mode, scoring, trace_budget, device):
-    res, cig = ends_free_align_batch([seq1], [seq2], [(0, 0)], mode=mode, scoring=scoring,
-                                     trace_budget=trace_budget, device=device)
+def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace_budget: int = 0,
+                          cigar: bool = True, device: int = 0):
+    """Local or semi-global alignment of a batch.  pairs: None (all-vs-all, db
+    outer / query inner) or (n, 2) (query index, db index).  Returns (results,
+    cigars): results is a structured array (score, status, q_begin, q_end,
+    db_begin, db_end, cigar_len; the ranges half-open and 0-based), cigars a
+    CigarBatch (pair k's [(length, op), ...]).  cigar=False runs the fill only:
+    score and ends, begins -1, no words.  A pair whose trace codes alone exceed
+    trace_budget bytes (0 selects 1 GiB per chunk) has status TRACE_CAP, its
+    score and ends, begins -1 and no words."""
+    return _align_batch("saln_ends_free_align_batch", queries, dbs, pairs, mode, scoring,
+                        trace_budget, cigar, device)
+
+
+def ends_free_align_long_batch(queries, dbs, pairs=None, *, mode, scoring=None,
+                               trace_budget: int = 0, cigar: bool = True, device: int = 0):
+    """ends_free_align_batch without the length limits
+    (saln_ends_free_long_align_batch): the same arguments and return.  A pair
+    of at most 1,024 x 65,000 runs as there and gives the same record and
+    words; every other pair runs the chunked fill.  The only limit is the
+    range guard."""
+    return _align_batch("saln_ends_free_long_align_batch", queries, dbs, pairs, mode, scoring,
+                        trace_budget, cigar, device)
+
+
+def _one(seq1, seq2, mode, scoring, trace_budget, device, batch=ends_free_align_batch):
+    res, cig = batch([seq1], [seq2], [(0, 0)], mode=mode, scoring=scoring,
+                     trace_budget=trace_budget, device=device)
     return res[0], cig[0]
 
 
@@ -103,6 +127,17 @@ def semi_global_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device
     """(result record, cigar) of the whole of seq1 (query) against the best
     window seq2[db_begin:db_end] of the db."""
     return _one(seq1, seq2, Mode.SemiGlobal, scoring, trace_budget, device)
+
+
+def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+    """local_align for sequences of any length (ends_free_align_long_batch)."""
+    return _one(seq1, seq2, Mode.Local, scoring, trace_budget, device, ends_free_align_long_batch)
+
+
+def semi_global_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+    """semi_global_align for sequences of any length (ends_free_align_long_batch)."""
+    return _one(seq1, seq2, Mode.SemiGlobal, scoring, trace_budget, device,
+                ends_free_align_long_batch)
 
 
 def cigar_score(cigar, scoring=None) -> int:
@@ -127,6 +162,26 @@ def trace_bytes(len_q: int, len_db: int) -> int:
     _lib.check(_lib.lib().saln_ends_free_trace_bytes(int(len_q), int(len_db), C.byref(out)),
                "saln_ends_free_trace_bytes")
     return out.value
+
+
+def trace_bytes_long(len_q: int, len_db: int) -> int:
+    """saln_ends_free_long_trace_bytes: bytes of trace codes of one pair under
+    ends_free_align_long_batch (host only); trace_bytes within its limits."""
+    out = C.c_uint64()
+    _lib.check(_lib.lib().saln_ends_free_long_trace_bytes(int(len_q), int(len_db), C.byref(out)),
+               "saln_ends_free_long_trace_bytes")
+    return out.value
+
+
+def pair_path_long(len_q: int, len_db: int) -> tuple[int, int]:
+    """saln_ends_free_long_pair_path: (long_fill, chunks) of one pair under
+    ends_free_align_long_batch (host only): 1 and its 1,024-column chunks when
+    it runs the chunked fill, (0, 1) when it runs a class fill."""
+    lf, chunks = C.c_int32(), C.c_uint32()
+    _lib.check(_lib.lib().saln_ends_free_long_pair_path(int(len_q), int(len_db), C.byref(lf),
+                                                        C.byref(chunks)),
+               "saln_ends_free_long_pair_path")
+    return lf.value, chunks.value
 
 
 def pair_geometry(len_q: int) -> tuple[int, int]:
