@@ -24,11 +24,14 @@ extern "C" {
 
 #define SALN_ABI_VERSION 1
 
-/* Mode — src/parse.rs:44-50 (declaration order Global, Local, SemiGlobal). */
+/* Mode — src/parse.rs:44-50 (declaration order Global, Local, SemiGlobal).
+ * SALN_MODE_OVERLAP is this library's own (the ends-free engine, below): no
+ * reference name, and 3 stays an unknown mode. */
 typedef enum {
     SALN_MODE_GLOBAL = 0,
     SALN_MODE_LOCAL = 1,
-    SALN_MODE_SEMI_GLOBAL = 2
+    SALN_MODE_SEMI_GLOBAL = 2,
+    SALN_MODE_OVERLAP = 4
 } saln_mode;
 
 /* Per-pair status and API return codes.  The reference returns
@@ -702,8 +705,9 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
                                   const uint64_t *len_db, uint64_t n_pairs,
                                   saln_wfa_affine_pass_geometry out[2]);
 
-/* ------------------------------- ends-free alignment: local and semi-global (new)
- * NOT a reference-parity path.  The reference only declares these modes:
+/* ------------------- ends-free alignment: local, semi-global and overlap (new)
+ * NOT a reference-parity path.  The reference only declares the first two modes
+ * (overlap, SALN_MODE_OVERLAP, has no reference name at all):
  * ScoreTensor::Local and ::SemiGlobal carry empty comments where the fill
  * should be (needleman_wunsch_affine.rs:238-239, :331-332) and n_w_align
  * answers "not implemented" (:433-434), which saln_nw_* and the CLI keep
@@ -721,7 +725,7 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  *   I(i,j) = max(I(i,j-1) + e, M(i,j-1) + o + e)      j >= 1
  *   D(i,j) = max(D(i-1,j) + e, M(i-1,j) + o + e)      i >= 1
  *   M(i,j) = s(i,j) + P(i-1,j-1)                      i, j >= 1
- *   P = max(M, I, D) (semi-global), max(0, M, I, D) (local);
+ *   P = max(M, I, D) (semi-global, overlap), max(0, M, I, D) (local);
  * everything no rule gives is -infinity.
  *  - SALN_MODE_SEMI_GLOBAL: the whole query against a free db substring.
  *    M(i,0) = 0 for every i (the start); M(0,j>0), I(i,0), D(i,0), D(0,j) are
@@ -732,11 +736,30 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  *  - SALN_MODE_LOCAL: score = max(0, max over i, j of M(i,j)); the alignment
  *    begins and ends with an M column; the smallest i, then the smallest j,
  *    wins a tie.  Score 0: no words, all four coordinates 0.
+ *  - SALN_MODE_OVERLAP (dovetail, all four ends free): a suffix of one
+ *    sequence against a prefix of the other, or one sequence inside the
+ *    other; no floor, no charge for the overhang on either sequence.
+ *    M(i,0) = 0 for i in 0..m and M(0,j) = 0 for j in 0..n (every cell of row
+ *    0 and column 0 is a free start); I(i,0), I(0,j), D(i,0), D(0,j) are
+ *    -infinity; by the rules I(i,1) = o + e for i >= 1 (it opens from M(i,0))
+ *    and D(1,j) = o + e for j >= 1 (it opens from M(0,j); semi-global's
+ *    D(1,j) is -infinity).  The end candidates are the border cells (i,n),
+ *    1 <= i <= m, and (m,j), 1 <= j <= n, each with the value P(i,j); score =
+ *    max(0, the best candidate).  No strictly positive candidate (n = 0 and
+ *    m = 0 included): the empty alignment, score 0, no words, all four
+ *    coordinates 0 (local's convention).  Else the end cell is the candidate
+ *    with the largest value, the smallest i, then the smallest j, winning a
+ *    tie (a last-column cell above row m beats a last-row cell), and the end
+ *    state is the first of M, I, D equal to P there.  At least one of
+ *    q_begin and db_begin is 0, at least one of q_end = n and db_end = m
+ *    holds.
  * The walk's choice among co-optimal paths is fixed.  In M at (i,j): emit
  * '=' or 'X', v = M(i,j) - s(i,j), go to (i-1,j-1); local stops when v == 0,
- * semi-global on reaching column 0; else the next state is the first of M,
- * I, D whose value there equals v.  In I or D extend comes before open.  A
- * pair's words depend on nothing but the pair and the scoring.
+ * semi-global on reaching column 0, overlap on reaching row 0 or column 0;
+ * else the next state is the first of M, I, D whose value there equals v.
+ * In I or D extend comes before open; overlap also stops after an 'I' that
+ * reaches column 0 or a 'D' that reaches row 0 (gaps opened from the free
+ * start).  A pair's words depend on nothing but the pair and the scoring.
  * Ranges are half-open and 0-based: the '=', 'X' and 'I' lengths sum to
  * q_end - q_begin, the '=', 'X' and 'D' lengths to db_end - db_begin.
  *
@@ -753,8 +776,9 @@ typedef struct {
 } saln_ends_free_result;              /* 32 bytes */
 
 /* Pair conventions and argument errors as saln_wfa_affine_align_batch (NULL
- * pair lists = all-vs-all, db outer).  mode: SALN_MODE_LOCAL or
- * SALN_MODE_SEMI_GLOBAL; SALN_MODE_GLOBAL is SALN_E_INVALID (use saln_nw_*).
+ * pair lists = all-vs-all, db outer).  mode: SALN_MODE_LOCAL,
+ * SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP; SALN_MODE_GLOBAL is
+ * SALN_E_INVALID (use saln_nw_*), and so is every other value.
  * want_cigar != 0: the fill stores 4-bit trace codes and the walk follows
  * them, in chunks: pairs are packed greedily in pair order into chunks of at
  * most trace_budget_bytes of codes (saln_ends_free_trace_bytes each; 0

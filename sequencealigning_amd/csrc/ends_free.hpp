@@ -94,23 +94,25 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
 }
 
 // Fill of pairs[first .. first + count), all of class cls with dbs of at most
-// ld_max rows.  codes == nullptr: score only.  end_state (with codes): the
-// state of each pair's end cell (0 M, 1 I), indexed like results.
-hipError_t launch_ef_fill(int cls, bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+// ld_max rows.  mode: SALN_MODE_LOCAL, _SEMI_GLOBAL or _OVERLAP (the host has
+// checked it).  codes == nullptr: score only.  end_state (with codes): the
+// state of each pair's end cell (0 M, 1 I), indexed like results; overlap's
+// walk takes it from the end cell's own code instead.
+hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
                           uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
                           hipStream_t s);
 // Chunked fill of pairs[first .. first + count) (any lengths): `slots` waves,
 // each with slot_rows (>= the longest db) 8-byte entries of bnd, taking pairs
 // from *counter, which the caller has zeroed on the stream.
-hipError_t launch_ef_fill_long(bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                                const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
                                uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s);
 // Walk of pairs[0 .. count): one pair per lane, from the end cell the fill
 // reported.  A pair's words end at words[cig_off + lq + ld), cigar_len of
 // them (also in lens, indexed like pairs).
-hipError_t launch_ef_walk(bool local, const EfPair *pairs, uint32_t count, const uint8_t *qs,
+hipError_t launch_ef_walk(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
                           const uint8_t *ds, const uint8_t *codes, const uint8_t *end_state,
                           saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
                           hipStream_t s);

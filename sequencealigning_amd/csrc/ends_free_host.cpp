@@ -1,7 +1,9 @@
-// C ABI of the ends-free engine (include/saln.h, saln_ends_free_*): local and
-// semi-global affine-gap alignment.  Not a reference-parity path - the
-// reference only declares these modes (needleman_wunsch_affine.rs:238-239,
-// :331-332, :433-434); the checker is the plain model tests/ends_free_model.py.
+// C ABI of the ends-free engine (include/saln.h, saln_ends_free_*): local,
+// semi-global and overlap affine-gap alignment.  Not a reference-parity path -
+// the reference only declares the first two modes
+// (needleman_wunsch_affine.rs:238-239, :331-332, :433-434) and has no overlap;
+// the checkers are the plain models tests/ends_free_model.py and
+// tests/overlap_model.py.
 //
 // A batch's pairs are grouped by query class (ef_class_of) and, within a
 // class, ordered by falling db length and cut where the length's power-of-two
@@ -58,7 +60,8 @@ void plan_launches(std::vector<EfPair> *pairs, std::vector<Launch> *out, bool lo
 }
 
 int check_mode(int32_t mode) {
-    if (mode == SALN_MODE_LOCAL || mode == SALN_MODE_SEMI_GLOBAL) return SALN_OK;
+    if (mode == SALN_MODE_LOCAL || mode == SALN_MODE_SEMI_GLOBAL || mode == SALN_MODE_OVERLAP)
+        return SALN_OK;
     if (mode == SALN_MODE_GLOBAL)
         set_error("ends_free: SALN_MODE_GLOBAL is not an ends-free mode; global alignment is "
                   "saln_nw_align / saln_nw_align_batch / saln_nw_plan_create");
@@ -143,19 +146,19 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
 
 // The fills of `pairs` (device copy d_pairs, in plan_launches' order).  ws:
 // the chunked fill's workspace (launches of kEfLongClass need one).
-int run_fills(const std::vector<Launch> &launches, bool local, const EfPair *d_pairs,
+int run_fills(const std::vector<Launch> &launches, int32_t mode, const EfPair *d_pairs,
               const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, uint8_t *d_codes,
               uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
               EfLongWorkspace *ws = nullptr) {
     for (const Launch &l : launches) {
         if (l.cls == kEfLongClass) {
             if (!ws) return SALN_E_INVALID;
-            const int rc = ef_long_fill(ws, local, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+            const int rc = ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
                                         d_codes, d_end_state, d_results, s);
             if (rc != SALN_OK) return rc;
             continue;
         }
-        HIP_TRY(launch_ef_fill(l.cls, local, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+        HIP_TRY(launch_ef_fill(l.cls, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
                                d_codes, d_end_state, d_results, s));
     }
     return SALN_OK;
@@ -166,7 +169,7 @@ int run_fills(const std::vector<Launch> &launches, bool local, const EfPair *d_p
 struct saln_ends_free_plan {
     saln_context *ctx = nullptr;
     EfScoring sc{};
-    bool local = false;
+    int32_t mode = SALN_MODE_LOCAL;
     uint64_t n = 0;
     std::vector<Launch> launches;
     DevBuf d_pairs;
@@ -215,7 +218,7 @@ int saln_ends_free_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_
     if (rc == SALN_OK)
         rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &pairs);
     if (rc != SALN_OK) return rc;
-    p->local = mode == SALN_MODE_LOCAL;
+    p->mode = mode;
     p->n = n_pairs;
     plan_launches(&pairs, &p->launches);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -233,7 +236,7 @@ int saln_ends_free_execute(saln_ends_free_plan *p, const uint8_t *d_q_seq, const
     if (!p->n) return SALN_OK;
     hipStream_t s = resolve_stream(stream, p->ctx);
     HIP_TRY(hipSetDevice(p->ctx->device));
-    return run_fills(p->launches, p->local, p->d_pairs.as<EfPair>(), d_q_seq, d_db_seq, p->sc,
+    return run_fills(p->launches, p->mode, p->d_pairs.as<EfPair>(), d_q_seq, d_db_seq, p->sc,
                      nullptr, nullptr, d_results, s);
 }
 
@@ -262,7 +265,6 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     if (rc == SALN_OK)
         rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all, long_ok);
     if (rc != SALN_OK) return rc;
-    const bool local = mode == SALN_MODE_LOCAL;
     auto aln = std::make_unique<saln_ends_free_aln>();
     aln->off.assign(n_pairs + 1, 0);
     if (n_pairs == 0) {
@@ -332,7 +334,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         plan_launches(&plain.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, plain.pairs.data(), plain.pairs.size() * sizeof(EfPair),
                                hipMemcpyHostToDevice, s));
-        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s,
+        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s,
                        &ws);
         if (rc != SALN_OK) return rc;
         HIP_TRY(hipStreamSynchronize(s));  // d_pairs and the host vector are reused
@@ -350,10 +352,10 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         // the fills and the walk read the same descriptors, in the fills' order
         plan_launches(&c.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, c.pairs.data(), n * sizeof(EfPair), hipMemcpyHostToDevice, s));
-        rc = run_fills(launches, local, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
+        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
                        d_state.as<uint8_t>(), results, s, &ws);
         if (rc != SALN_OK) return rc;
-        HIP_TRY(launch_ef_walk(local, d_pairs.as<EfPair>(), n, sq, sd, d_codes.as<uint8_t>(),
+        HIP_TRY(launch_ef_walk(mode, d_pairs.as<EfPair>(), n, sq, sd, d_codes.as<uint8_t>(),
                                d_state.as<uint8_t>(), results, d_words.as<uint32_t>(),
                                d_lens.as<uint32_t>(), s));
         lens.resize(n);

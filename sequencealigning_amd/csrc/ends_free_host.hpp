@@ -26,7 +26,7 @@ struct EfLongWorkspace {
 
 // One chunked-fill launch of pairs[first .. first + count) with dbs of at most
 // ld_max rows: ef_long_slots waves.  ends_free_long_host.cpp.
-int ef_long_fill(EfLongWorkspace *ws, bool local, const EfPair *d_pairs, uint32_t first,
+int ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint32_t first,
                  uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
                  const EfScoring &sc, uint8_t *d_codes, uint8_t *d_end_state,
                  saln_ends_free_result *d_results, hipStream_t s);

@@ -1,8 +1,9 @@
 // Kernels of the ends-free engine (include/saln.h, saln_ends_free_*): Gotoh
-// affine-gap alignment with free ends, local (Smith-Waterman) and semi-global
-// (the whole query against a free db substring).  NOT a reference-parity
-// path: the reference only declares these modes.  DESIGN.md section 3 holds
-// the recurrences, the tie rules and the code layout.
+// affine-gap alignment with free ends, local (Smith-Waterman), semi-global
+// (the whole query against a free db substring) and overlap (dovetail: all
+// four ends free, no floor).  NOT a reference-parity path: the reference only
+// declares the first two modes.  DESIGN.md section 3 holds the recurrences,
+// the tie rules and the code layout.
 //
 // Fill: the decomposition of the NW i32 lane fill.  One pair per group of G
 // lanes, K query columns per lane in registers, the rows skewed over the
@@ -28,13 +29,15 @@ struct __attribute__((packed, aligned((K / 2) % 8 == 0 ? 8 : (K / 2) % 4 == 0 ? 
     uint8_t b[K / 2];
 };
 
-template <int G, int K, bool kLocal, bool kCodes>
+// kMode: SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
+template <int G, int K, int kMode, bool kCodes>
 __global__ __launch_bounds__(256) void ef_fill_kernel(
     const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
     uint32_t ld_max) {
     static_assert(K % 2 == 0, "two cells per code byte");
+    constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     const int gpb = (int)blockDim.x / G;
     const int lane = (int)threadIdx.x % G, grp = (int)threadIdx.x / G;
     const uint32_t gi = blockIdx.x * (uint32_t)gpb + (uint32_t)grp;
@@ -47,7 +50,7 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     res.status = SALN_OK;
     res.q_begin = res.db_begin = -1;
     res.cigar_len = res.reserved = 0;
-    if (lq == 0) {  // no column: score 0 at the origin in both modes
+    if (lq == 0) {  // no column: score 0 at the origin in every mode
         if (lane == 0) {
             res.score = res.q_end = res.db_end = 0;
             results[p.out] = res;
@@ -72,21 +75,24 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     for (int k = 0; k < K; ++k) {
         const uint32_t j = col0 + k + 1;
         qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
-        // row 0: semi-global P(0, j) = I(0, j) = o + j e; local P = 0
-        Hp[k] = kLocal ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
-        Dn[k] = kEfNeg;  // D(1, j): M(0, j) and D(0, j) are -inf
+        // row 0: semi-global P(0, j) = I(0, j) = o + j e; local and overlap P = 0
+        Hp[k] = kLocal || kOverlap ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
+        // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
+        Dn[k] = kOverlap ? o + e : kEfNeg;
     }
-    int32_t hd = kLocal || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;  // P(0, col0)
-    // column 0, entering lane 0: P(i, 0) = 0 in both modes (semi-global's
-    // free start, local's floor); I(i, 1) opens from M(i, 0) = 0 in
-    // semi-global and is -inf in local
+    int32_t hd = kLocal || kOverlap || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;  // P(0, col0)
+    // column 0, entering lane 0: P(i, 0) = 0 in every mode (the free start of
+    // semi-global and overlap, local's floor); I(i, 1) opens from M(i, 0) = 0
+    // in semi-global and overlap and is -inf in local
     const int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
     int32_t pubF = kEfNeg, pubH = kEfNeg;
     // best end cell of my columns: local every M(i, j), strictly positive;
-    // semi-global max(M, I)(i, lq) in the lane holding column lq, row 0 first
-    int32_t best = kLocal ? 0 : o + (int32_t)lq * e;
+    // semi-global max(M, I)(i, lq) in the lane holding column lq, row 0 first;
+    // overlap P(i, lq) in that lane, strictly positive (the last row's
+    // candidates are taken from Hp after the loop)
+    int32_t best = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
     uint32_t best_i = 0, best_k = 0;  // semi-global: best_k is the end state
-    if (!kLocal) best_k = 1;          // row 0 ends in I
+    if (!kLocal && !kOverlap) best_k = 1;  // row 0 ends in I
     uint8_t *crow = nullptr;
     if constexpr (kCodes) crow = codes + p.code_off + (size_t)lane * (K / 2);
     const int T = (int)ld + G - 1;
@@ -120,6 +126,8 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
                     best = b ? M : best;
                     best_i = b ? (uint32_t)r : best_i;
                     best_k = b ? (uint32_t)k : best_k;
+                } else if constexpr (kOverlap) {
+                    Msel = (uint32_t)k == k_end ? P3 : Msel;  // P(r, my k_end-th column)
                 } else {
                     Msel = (uint32_t)k == k_end ? M : Msel;
                     Isel = (uint32_t)k == k_end ? I : Isel;
@@ -132,7 +140,11 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
             hd = inH;
             pubF = F;
             pubH = Hp[K - 1];
-            if constexpr (!kLocal) {
+            if constexpr (kOverlap) {
+                const bool b = Msel > best;  // the smallest row wins a tie
+                best = b ? Msel : best;
+                best_i = b ? (uint32_t)r : best_i;
+            } else if constexpr (!kLocal) {
                 const int32_t v = max(Msel, Isel);
                 const bool b = v > best;  // the smallest row wins a tie
                 best = b ? v : best;
@@ -149,7 +161,29 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
             }
         }
     }
-    if constexpr (kLocal) {
+    if constexpr (kOverlap) {
+        // Only the lane of column lq tracked a last-column cell.  The last
+        // row: Hp holds P(ld, j) of my columns (row 0's zeros when ld == 0).
+        // Strict > from 0 over rising columns keeps the smallest column; pad
+        // columns hold real-looking values and are masked out.
+        if ((uint32_t)lane != l_end) best = 0;
+        best_k = k_end;
+        int32_t rbest = 0;
+        uint32_t rbest_k = 0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const bool b = col0 + (uint32_t)k + 1 <= lq && Hp[k] > rbest;
+            rbest = b ? Hp[k] : rbest;
+            rbest_k = b ? (uint32_t)k : rbest_k;
+        }
+        // a last-column cell above row ld wins a tie with a last-row cell; in
+        // row ld it is the corner, and the last row's smallest column wins
+        const bool row = rbest > best || (rbest == best && best_i == ld);
+        best = row ? rbest : best;
+        best_i = row ? ld : best_i;
+        best_k = row ? rbest_k : best_k;
+    }
+    if constexpr (kLocal || kOverlap) {
         // the group's best: the largest value, then the smallest row, then
         // the smallest column (lanes met a row at different steps: the row
         // index decides, not the step).  Lanes without a positive cell hold
@@ -181,7 +215,7 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
 
 // One pair per lane.  Words are written back to front so that they end at
 // the end of the pair's area in forward order.
-template <bool kLocal>
+template <int kMode>
 __global__ __launch_bounds__(64) void ef_walk_kernel(
     const EfPair *__restrict__ pairs, uint32_t count, const uint8_t *__restrict__ qs,
     const uint8_t *__restrict__ ds, const uint8_t *__restrict__ codes,
@@ -197,6 +231,7 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
     uint32_t *w = words + p.cig_off;
     // the fill's end cell, kept inside the matrix whatever the record holds
     uint32_t i = min((uint32_t)max(res.db_end, 0), p.ld), j = min((uint32_t)max(res.q_end, 0), p.lq);
+    constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     uint32_t st = end_state[p.out] & 1u;  // 0 M, 1 I, 2 D
     uint32_t n = 0, run = 0, op = 0;
     auto emit = [&](uint32_t o, uint32_t len) {
@@ -209,8 +244,32 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
         op = o;
         run = len;
     };
-    if (kLocal && res.score <= 0) i = j = 0;
+    if ((kLocal || kOverlap) && res.score <= 0) i = j = 0;
+    if constexpr (kOverlap) {
+        // the end state is the end cell's own code: the first of M, I, D equal to P
+        if (i > 0 && j > 0) st = ef_code(codes, p, i, j) & kEfArgMask;
+    }
     while (j > 0) {
+        if constexpr (kOverlap) {
+            // every cell of row 0 and column 0 is a free start: the walk ends
+            // as soon as it stands on one, in M or after a gap that opened there
+            if (i == 0) break;
+            if (st == 0) {
+                emit(q[j - 1] == d[i - 1] ? SALN_CIGAR_EQ : SALN_CIGAR_X, 1);
+                --i, --j;
+                if (i == 0 || j == 0) break;
+                st = ef_code(codes, p, i, j) & kEfArgMask;
+            } else if (st == 1) {
+                emit(SALN_CIGAR_I, 1);
+                --j;  // column 0: I(i, 1) opened from M(i, 0)
+                st = j > 0 && (ef_code(codes, p, i, j) & kEfIExt) ? 1u : 0u;
+            } else {
+                emit(SALN_CIGAR_D, 1);
+                --i;  // row 0: D(1, j) opened from M(0, j)
+                st = i > 0 && (ef_code(codes, p, i, j) & kEfDExt) ? 2u : 0u;
+            }
+            continue;
+        }
         if (i == 0) {  // semi-global row 0: the rest of the query is one insertion
             if (!kLocal) emit(SALN_CIGAR_I, j);
             j = 0;
@@ -264,7 +323,7 @@ __global__ __launch_bounds__(256) void ef_gather_kernel(
 namespace {
 
 template <int G, int K>
-hipError_t fill_class(bool local, bool with_codes, dim3 grid, dim3 block, size_t lds, hipStream_t s,
+hipError_t fill_class(int32_t mode, bool with_codes, dim3 grid, dim3 block, size_t lds, hipStream_t s,
                       const EfPair *pairs, uint32_t first, uint32_t count, const uint8_t *qs,
                       const uint8_t *ds, uint8_t *codes, uint8_t *end_state,
                       saln_ends_free_result *results, EfScoring sc, uint32_t ld_max) {
@@ -273,13 +332,16 @@ hipError_t fill_class(bool local, bool with_codes, dim3 grid, dim3 block, size_t
                            results, sc, ld_max);
         return hipGetLastError();
     };
-    if (local) return with_codes ? go(ef_fill_kernel<G, K, true, true>) : go(ef_fill_kernel<G, K, true, false>);
-    return with_codes ? go(ef_fill_kernel<G, K, false, true>) : go(ef_fill_kernel<G, K, false, false>);
+    constexpr int kL = SALN_MODE_LOCAL, kS = SALN_MODE_SEMI_GLOBAL, kO = SALN_MODE_OVERLAP;
+    if (mode == kL) return with_codes ? go(ef_fill_kernel<G, K, kL, true>) : go(ef_fill_kernel<G, K, kL, false>);
+    if (mode == kO) return with_codes ? go(ef_fill_kernel<G, K, kO, true>) : go(ef_fill_kernel<G, K, kO, false>);
+    if (mode != kS) return hipErrorInvalidValue;
+    return with_codes ? go(ef_fill_kernel<G, K, kS, true>) : go(ef_fill_kernel<G, K, kS, false>);
 }
 
 }  // namespace
 
-hipError_t launch_ef_fill(int cls, bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
                           uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
                           hipStream_t s) {
@@ -293,25 +355,30 @@ hipError_t launch_ef_fill(int cls, bool local, const EfPair *pairs, uint32_t fir
     const dim3 grid((count + groups - 1) / groups), block(groups * G);
     const bool wc = codes != nullptr;
     switch (cls) {
-        case 0: return fill_class<16, 10>(local, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        case 1: return fill_class<16, 16>(local, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        case 2: return fill_class<64, 8>(local, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        default: return fill_class<64, 16>(local, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
+        case 0: return fill_class<16, 10>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
+        case 1: return fill_class<16, 16>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
+        case 2: return fill_class<64, 8>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
+        default: return fill_class<64, 16>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
     }
 }
 
-hipError_t launch_ef_walk(bool local, const EfPair *pairs, uint32_t count, const uint8_t *qs,
+hipError_t launch_ef_walk(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
                           const uint8_t *ds, const uint8_t *codes, const uint8_t *end_state,
                           saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
                           hipStream_t s) {
     if (count == 0) return hipSuccess;
     const dim3 grid((count + 63) / 64), block(64);
-    if (local)
-        hipLaunchKernelGGL(ef_walk_kernel<true>, grid, block, 0, s, pairs, count, qs, ds, codes,
-                           end_state, results, words, lens);
+    if (mode == SALN_MODE_LOCAL)
+        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_LOCAL>, grid, block, 0, s, pairs, count, qs, ds,
+                           codes, end_state, results, words, lens);
+    else if (mode == SALN_MODE_OVERLAP)
+        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_OVERLAP>, grid, block, 0, s, pairs, count, qs, ds,
+                           codes, end_state, results, words, lens);
+    else if (mode == SALN_MODE_SEMI_GLOBAL)
+        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_SEMI_GLOBAL>, grid, block, 0, s, pairs, count, qs,
+                           ds, codes, end_state, results, words, lens);
     else
-        hipLaunchKernelGGL(ef_walk_kernel<false>, grid, block, 0, s, pairs, count, qs, ds, codes,
-                           end_state, results, words, lens);
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

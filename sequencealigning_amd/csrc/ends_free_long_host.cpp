@@ -11,7 +11,7 @@
 
 using namespace saln;
 
-int saln::ef_long_fill(EfLongWorkspace *ws, bool local, const EfPair *d_pairs, uint32_t first,
+int saln::ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint32_t first,
                        uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
                        const EfScoring &sc, uint8_t *d_codes, uint8_t *d_end_state,
                        saln_ends_free_result *d_results, hipStream_t s) {
@@ -25,7 +25,7 @@ int saln::ef_long_fill(EfLongWorkspace *ws, bool local, const EfPair *d_pairs, u
     }
     if (!ws->counter.p) HIP_TRY(ws->counter.alloc(16));
     HIP_TRY(hipMemsetAsync(ws->counter.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(launch_ef_fill_long(local, d_pairs, first, count, d_q, d_db, sc, d_codes, d_end_state,
+    HIP_TRY(launch_ef_fill_long(mode, d_pairs, first, count, d_q, d_db, sc, d_codes, d_end_state,
                                 d_results, ws->bnd.p, slot_rows, slots, ws->counter.as<uint32_t>(), s));
     return SALN_OK;
 }

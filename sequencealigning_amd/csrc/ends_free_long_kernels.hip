@@ -19,7 +19,11 @@
 //  - local's best cell: a best per chunk on strict > (rows rise inside a
 //    chunk), merged into the running best on (value, row) at the chunk's end,
 //    and a final reduction over the lanes on (value, row, column) in full
-//    32-bit words.
+//    32-bit words;
+//  - overlap's end cell: the owner of column n (in the last chunk) keeps the
+//    best P(r, n) as semi-global's does; every lane takes the last row's
+//    candidates from Hp after each chunk's last row, merged on strict > so
+//    that an earlier chunk keeps the smaller column; then local's reduction.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -44,13 +48,14 @@ static_assert(kLanes * kCols == (int)kEfChunkCols, "a chunk is one 64 x 16 fill"
 // runs at most 128 steps earlier) and written by lane 63 at step r + 62, both
 // by this wave in program order, so a row's old value is always consumed
 // before its new one is stored.
-template <bool kLocal, bool kCodes>
+template <int kMode, bool kCodes>
 __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
     int2 *bnd, uint64_t slot_rows, uint32_t *counter) {
     constexpr int K = kCols;
+    constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     __shared__ uint8_t ring[kRing];
     const int lane = (int)threadIdx.x;
     int2 *col = bnd + (size_t)blockIdx.x * slot_rows;
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         res.status = SALN_OK;
         res.q_begin = res.db_begin = -1;
         res.cigar_len = res.reserved = 0;
-        if (lq == 0) {  // no column: score 0 at the origin in both modes
+        if (lq == 0) {  // no column: score 0 at the origin in every mode
             if (lane == 0) {
                 res.score = res.q_end = res.db_end = 0;
                 results[p.out] = res;
@@ -81,9 +86,13 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         // the lane and register of column lq in the last chunk
         const uint32_t l_end = jend % (uint32_t)kEfChunkCols / K, k_end = jend % K;
         // running best.  local: best_j is the absolute column.  semi-global:
-        // the single owner restarts from row 0 in every chunk, the last counts
-        int32_t best = kLocal ? 0 : o + (int32_t)lq * e;
+        // the single owner restarts from row 0 in every chunk, the last counts.
+        // overlap: the owner of column lq as semi-global's (strictly positive
+        // cells only), and rbest / rbest_j, the best of the last row so far
+        int32_t best = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
         uint32_t best_i = 0, best_j = 0, best_st = kLocal ? 0u : 1u;  // row 0 ends in I
+        int32_t rbest = 0;
+        uint32_t rbest_j = 0;
         const int T = ld ? (int)ld + kLanes - 1 : 0;  // no row: the row-0 values stand
         for (uint32_t c = 0; c < nchunks; ++c) {
             const uint32_t col0 = c * (uint32_t)kEfChunkCols + (uint32_t)lane * K;  // my columns: col0+1 .. col0+K
@@ -94,18 +103,18 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
             for (int k = 0; k < K; ++k) {
                 const uint32_t j = col0 + k + 1;
                 qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
-                Hp[k] = kLocal ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
-                Dn[k] = kEfNeg;
+                Hp[k] = kLocal || kOverlap ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
+                Dn[k] = kOverlap ? o + e : kEfNeg;  // overlap: D(1, j) opens from M(0, j) = 0
             }
             // P(0, col0), by the absolute column: also lane 0 of a chunk c > 0
-            int32_t hd = kLocal || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
+            int32_t hd = kLocal || kOverlap || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
             int32_t pubF = kEfNeg, pubH = kEfNeg;
             // this chunk's best of my columns, as ef_fill_kernel keeps it: rows
             // rise inside a chunk, so strict > keeps the smallest row, then
             // the smallest column.  (Local pad columns need no mask: a pad
             // cell's M lies strictly below some real M of the pair, so it can
             // only displace a lane's value that is not the pair's best.)
-            int32_t cbest = kLocal ? 0 : o + (int32_t)lq * e;
+            int32_t cbest = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
             uint32_t cbest_i = 0, cbest_k = kLocal ? 0u : 1u;  // semi-global: cbest_k is the end state
             uint8_t *crow = nullptr;
             if constexpr (kCodes) crow = codes + p.code_off + (size_t)c * (kEfChunkCols / 2) + (size_t)lane * (K / 2);
@@ -135,9 +144,9 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                     const int s = t - t0;
                     const int r = t - lane + 1;
                     const uint32_t dch = ring[(uint32_t)(t - lane) & (kRing - 1)];  // d[r-1]
-                    // column c0 entering lane 0.  Chunk 0: P(i, 0) = 0 in both
-                    // modes, I(i, 1) opens from M(i, 0) = 0 in semi-global and is
-                    // -inf in local.  Later chunks: what lane 63 published for row t + 1
+                    // column c0 entering lane 0.  Chunk 0: P(i, 0) = 0 in every
+                    // mode, I(i, 1) opens from M(i, 0) = 0 in semi-global and overlap
+                    // and is -inf in local.  Later chunks: what lane 63 published for row t + 1
                     int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
                     if (c > 0) {
                         bH = __builtin_amdgcn_readlane(bcur.x, s);
@@ -171,6 +180,8 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                                 cbest = b ? M : cbest;
                                 cbest_i = b ? (uint32_t)r : cbest_i;
                                 cbest_k = b ? (uint32_t)k : cbest_k;
+                            } else if constexpr (kOverlap) {
+                                Msel = (uint32_t)k == k_end ? P3 : Msel;  // P(r, my k_end-th column)
                             } else {
                                 Msel = (uint32_t)k == k_end ? M : Msel;
                                 Isel = (uint32_t)k == k_end ? I : Isel;
@@ -184,7 +195,11 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                         pubF = F;
                         pubH = Hp[K - 1];
                         if (publish) col[r - 1] = make_int2(pubH, pubF);
-                        if constexpr (!kLocal) {
+                        if constexpr (kOverlap) {
+                            const bool b = Msel > cbest;  // the smallest row wins a tie
+                            cbest = b ? Msel : cbest;
+                            cbest_i = b ? (uint32_t)r : cbest_i;
+                        } else if constexpr (!kLocal) {
                             const int32_t v = max(Msel, Isel);
                             const bool b = v > cbest;  // the smallest row wins a tie
                             cbest = b ? v : cbest;
@@ -205,13 +220,37 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                 best = take ? cbest : best;
                 best_i = take ? cbest_i : best_i;
                 best_j = take ? col0 + cbest_k + 1 : best_j;
+            } else if constexpr (kOverlap) {
+                best = cbest;  // the last chunk's counts, in the lane of column lq
+                best_i = cbest_i;
+                // the last row of this chunk: Hp holds P(ld, j) of my columns
+                // (row 0's zeros when ld == 0), pad columns masked out.  Strict >
+                // over rising columns and chunks keeps the smallest column
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const uint32_t j = col0 + (uint32_t)k + 1;
+                    const bool b = j <= lq && Hp[k] > rbest;
+                    rbest = b ? Hp[k] : rbest;
+                    rbest_j = b ? j : rbest_j;
+                }
             } else {
                 best = cbest;
                 best_i = cbest_i;
                 best_st = cbest_k;
             }
         }
-        if constexpr (kLocal) {
+        if constexpr (kOverlap) {
+            // only the lane of column lq (of the last chunk) tracked it.  A
+            // last-column cell above row ld wins a tie with a last-row cell;
+            // in row ld it is the corner, and the last row's smallest column wins
+            if ((uint32_t)lane != l_end) best = 0;
+            best_j = lq;
+            const bool row = rbest > best || (rbest == best && best_i == ld);
+            best = row ? rbest : best;
+            best_i = row ? ld : best_i;
+            best_j = row ? rbest_j : best_j;
+        }
+        if constexpr (kLocal || kOverlap) {
             // the wave's best: the largest value, then the smallest row, then
             // the smallest column.  Lanes without a positive cell lose.
             uint32_t bi = best > 0 ? best_i : 0xFFFFFFFFu, bj = best_j;
@@ -244,7 +283,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     }
 }
 
-hipError_t launch_ef_fill_long(bool local, const EfPair *pairs, uint32_t first, uint32_t count,
+hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                                const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
                                uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s) {
@@ -255,8 +294,11 @@ hipError_t launch_ef_fill_long(bool local, const EfPair *pairs, uint32_t first, 
                            end_state, results, sc, static_cast<int2 *>(bnd), slot_rows, counter);
         return hipGetLastError();
     };
-    if (local) return codes ? go(ef_fill_long_kernel<true, true>) : go(ef_fill_long_kernel<true, false>);
-    return codes ? go(ef_fill_long_kernel<false, true>) : go(ef_fill_long_kernel<false, false>);
+    constexpr int kL = SALN_MODE_LOCAL, kS = SALN_MODE_SEMI_GLOBAL, kO = SALN_MODE_OVERLAP;
+    if (mode == kL) return codes ? go(ef_fill_long_kernel<kL, true>) : go(ef_fill_long_kernel<kL, false>);
+    if (mode == kO) return codes ? go(ef_fill_long_kernel<kO, true>) : go(ef_fill_long_kernel<kO, false>);
+    if (mode != kS) return hipErrorInvalidValue;
+    return codes ? go(ef_fill_long_kernel<kS, true>) : go(ef_fill_long_kernel<kS, false>);
 }
 
 }  // namespace saln

@@ -1,5 +1,5 @@
-"""Ends-free affine-gap alignment: local and semi-global — a separately
-labelled engine, NOT reference parity.
+"""Ends-free affine-gap alignment: local, semi-global and overlap — a
+separately labelled engine, NOT reference parity.
 
 The reference only declares these modes (``ScoreTensor::Local`` /
 ``::SemiGlobal`` carry empty comments, needleman_wunsch_affine.rs:238-239,
@@ -13,13 +13,19 @@ against a db base; the db is the reference sequence).
 
 * ``Mode.Local``: the best-scoring pair of substrings (Smith-Waterman).
 * ``Mode.SemiGlobal``: the whole query against a free db substring.
+* ``OVERLAP`` (4, this engine's own: ``records.Mode`` mirrors the reference's
+  three names): overlap (dovetail) alignment, all four ends free and no floor.
+  A suffix of one sequence against a prefix of the other, or one sequence
+  inside the other; no overlap with a positive score gives the empty
+  alignment (score 0, no words, coordinates 0).
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
-include/saln.h and DESIGN.md; the checker is tests/ends_free_model.py.
+include/saln.h and DESIGN.md; the checkers are tests/ends_free_model.py and
+tests/overlap_model.py.
 
 ``ends_free_align_batch`` and its one-pair forms take a query of at most
 1,024 columns and a db of at most 65,000 rows.  ``ends_free_align_long_batch``,
-``local_align_long`` and ``semi_global_align_long`` take pairs of any length
+``local_align_long``, ``semi_global_align_long`` and ``overlap_align_long`` take pairs of any length
 within the range guard ((n + m + 2) * max|parameter| < 2^30): a pair above the
 limits runs the chunked fill (ends_free_long_kernels.hip), every other pair
 the same fills as before, with the same records and words.
@@ -37,6 +43,7 @@ from .records import Mode
 DEFAULT_SCORING = (5, -4, -8, -6)
 TRACE_CAP = _lib.TRACE_CAP    # per-pair status: trace codes larger than the whole budget
 MAX_QUERY = 1024              # longest query (columns); saln_ends_free_pair_geometry
+OVERLAP = 4                   # SALN_MODE_OVERLAP: a mode value, not a records.Mode member
 
 
 def _mode(mode) -> int:
@@ -88,7 +95,8 @@ def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar,
 
 def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace_budget: int = 0,
                           cigar: bool = True, device: int = 0):
-    """Local or semi-global alignment of a batch.  pairs: None (all-vs-all, db
+    """Local, semi-global or overlap (mode=OVERLAP) alignment of a batch.
+    pairs: None (all-vs-all, db
     outer / query inner) or (n, 2) (query index, db index).  Returns (results,
     cigars): results is a structured array (score, status, q_begin, q_end,
     db_begin, db_end, cigar_len; the ranges half-open and 0-based), cigars a
@@ -129,6 +137,14 @@ def semi_global_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device
     return _one(seq1, seq2, Mode.SemiGlobal, scoring, trace_budget, device)
 
 
+def overlap_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+    """(result record, cigar) of the best overlap (dovetail) alignment of seq1
+    (query) and seq2 (db): seq1[q_begin:q_end] against seq2[db_begin:db_end],
+    each range touching an end of its sequence; score 0 and no words when no
+    overlap scores above 0."""
+    return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device)
+
+
 def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
     """local_align for sequences of any length (ends_free_align_long_batch)."""
     return _one(seq1, seq2, Mode.Local, scoring, trace_budget, device, ends_free_align_long_batch)
@@ -138,6 +154,11 @@ def semi_global_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, d
     """semi_global_align for sequences of any length (ends_free_align_long_batch)."""
     return _one(seq1, seq2, Mode.SemiGlobal, scoring, trace_budget, device,
                 ends_free_align_long_batch)
+
+
+def overlap_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+    """overlap_align for sequences of any length (ends_free_align_long_batch)."""
+    return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device, ends_free_align_long_batch)
 
 
 def cigar_score(cigar, scoring=None) -> int:

@@ -1,0 +1,525 @@
+"""GPU: the ends-free engine's overlap (dovetail) mode, SALN_MODE_OVERLAP = 4,
+through both fills (ends_free_kernels.hip, ends_free_long_kernels.hip), the
+walk, the batch code and the device-resident plan.  Every comparison is exact
+against the plain model (overlap_model.py): the whole result record and the
+CIGAR, word for word.  The inputs' preconditions are asserted from the model
+where the inputs are built."""
+import random
+
+import numpy as np
+import pytest
+
+import overlap_model as model
+
+pytestmark = pytest.mark.gpu
+
+OVERLAP = model.OVERLAP
+SCHEMES = [(5, -4, -8, -6), (1, -1, 0, -1), (2, -3, -5, -2), (4, -9, 0, -1)]
+HARSH = SCHEMES[3]          # a mismatch is worse than a one-column gap
+TRACE_CAP = 8
+ZERO = (0, 0, 0, 0, 0, 0, 0, 0)
+U = b"ACGTTGCAAGGCTA"       # 14 bases that match nothing in a run of N or R
+
+
+def _rand(rng, n, alphabet=b"ACGT"):
+    return bytes(rng.choice(alphabet) for _ in range(n))
+
+
+def _mutated(rng, src, sub=0.05, indel=0.02):
+    """src with substitutions and a few short indels."""
+    out = bytearray()
+    i = 0
+    while i < len(src):
+        u = rng.random()
+        if u < sub:
+            out.append(rng.choice(b"ACGT".replace(bytes([src[i]]), b"")))
+            i += 1
+        elif u < sub + indel / 2:
+            i += rng.randint(1, 3)                  # deletion
+        elif u < sub + indel:
+            out += _rand(rng, rng.randint(1, 3))    # insertion
+        else:
+            out.append(src[i])
+            i += 1
+    return bytes(out)
+
+
+_expected = {}   # (q, d, scheme) -> (Alignment, info): every model run happens once
+
+
+def _model(q, d, scheme=None):
+    key = (q, d, scheme)
+    if key not in _expected:
+        info = {}
+        _expected[key] = (model.align(q, d, scheme, info=info), info)
+    return _expected[key]
+
+
+def _expect(q, d, scheme=None):
+    a, _ = _model(q, d, scheme)
+    return a.record(), model.cigar_words(a.cigar)
+
+
+def _score_only(rec, status=0):
+    """The record of a pair whose walk did not run."""
+    return (rec[0], status, -1, rec[3], -1, rec[5], 0, 0)
+
+
+def _compare(saln, qs, ds, pairs, scheme=None, long=False, **kw):
+    """Runs one batch and compares every pair with the model."""
+    run = saln.ends_free_align_long_batch if long else saln.ends_free_align_batch
+    res, cig = run(qs, ds, pairs, mode=OVERLAP, scoring=scheme, **kw)
+    plist = pairs if pairs is not None else [(a, b) for b in range(len(ds)) for a in range(len(qs))]
+    assert len(res) == len(cig) == len(plist)
+    for k, (a, b) in enumerate(plist):
+        rec, words = _expect(qs[a], ds[b], scheme)
+        assert tuple(int(v) for v in res[k]) == rec, (k, len(qs[a]), len(ds[b]), qs[a][:40], ds[b][:40])
+        assert cig.words(k).tolist() == words, (k, len(qs[a]), len(ds[b]), qs[a][:40], ds[b][:40])
+    return res, cig
+
+
+# ------------------------------------------------------------------ 1. hand KATs
+KATS = [
+    (b"TTTTACGTA", b"ACGTACCCC"),        # 0 a query suffix over a db prefix
+    (b"ACGTACCCC", b"TTTTACGTA"),        # 1 a db suffix over a query prefix
+    (b"ACGTAC", b"GGGACGTACGGG"),        # 2 the query inside the db
+    (b"GGGACGTACGGG", b"ACGTAC"),        # 3 the db inside the query
+    (b"ACGTACGT", b"ACGTACGT"),          # 4 identical
+    (b"AAAA", b"CCCCCC"),                # 5 no positive overlap
+    (b"", b"ACGT"), (b"ACGT", b""), (b"", b""),      # 6 7 8
+    (b"A", b"A"), (b"A", b"C"),          # 9 10
+    (b"ACTTTTAC", b"ACGGGGAC"),          # 11 last column against last row: the smaller row
+    (b"ACTAC", b"AC"), (b"AC", b"ACTAC"),            # 12 13 ties within one border
+    (b"ACGNNNGT", b"TTACGNNNGT"),        # 14 N equals N
+]
+
+
+def test_hand_kats(saln):
+    qs = [q for q, _ in KATS]
+    ds = [d for _, d in KATS]
+    res, cig = _compare(saln, qs, ds, [(k, k) for k in range(len(KATS))])
+    rec = [tuple(int(v) for v in r) for r in res]
+    assert rec[0] == (25, 0, 4, 9, 0, 5, 1, 0) and cig[0] == [(5, "=")]
+    assert rec[1] == (25, 0, 0, 5, 4, 9, 1, 0)
+    assert rec[2] == (30, 0, 0, 6, 3, 9, 1, 0) and rec[3] == (30, 0, 3, 9, 0, 6, 1, 0)
+    assert rec[4] == (40, 0, 0, 8, 0, 8, 1, 0)
+    for k in (5, 6, 7, 8, 10):
+        assert rec[k] == ZERO and cig[k] == []
+    assert rec[9] == (5, 0, 0, 1, 0, 1, 1, 0)
+    assert rec[11] == (10, 0, 6, 8, 0, 2, 1, 0)
+    assert rec[12] == rec[13] == (10, 0, 0, 2, 0, 2, 1, 0)
+
+
+def test_hand_kats_gap_states(saln):
+    """The model test's hand cases of the harsh scheme: end states I and D,
+    and the walks that leave through a gap opened from the free start."""
+    cases = [(b"ACA", b"CC", [(1, "="), (1, "I")]), (b"AAA", b"CCAC", [(1, "="), (1, "D")]),
+             (b"AA", b"CAC", [(1, "I"), (1, "=")]), (b"AAA", b"CAC", [(1, "D"), (1, "=")])]
+    qs, ds = [c[0] for c in cases], [c[1] for c in cases]
+    _, cig = _compare(saln, qs, ds, [(k, k) for k in range(4)], HARSH)
+    assert [cig[k] for k in range(4)] == [c[2] for c in cases]
+
+
+def test_one_pair_forms(saln):
+    for fn in (saln.overlap_align, saln.overlap_align_long):
+        rec, cigar = fn(*KATS[0])
+        assert tuple(int(v) for v in rec) == (25, 0, 4, 9, 0, 5, 1, 0) and cigar == [(5, "=")]
+    q = _rand(random.Random(5), 1100)
+    rec, cigar = saln.overlap_align_long(q, q[1000:] + b"N" * 30)
+    assert tuple(int(v) for v in rec) == (500, 0, 1000, 1100, 0, 100, 1, 0) and cigar == [(100, "=")]
+
+
+# ------------------------------------------------ 2. random dovetails and containments
+def _lane_of(saln, n, j):
+    return (j - 1) // saln.ends_free.pair_geometry(n)[1]
+
+
+def _make_random_batch():
+    rng = random.Random(0x0E7A)
+    pairs = []
+    for _ in range(110):
+        base = _rand(rng, 400)
+        a, b = rng.randint(1, 200), rng.randint(1, 200)
+        kind = rng.randrange(6)
+        if kind == 0:      # query suffix over db prefix
+            ov = rng.randint(1, min(a, b))
+            x = base[:a]
+            q, d = x, x[a - ov:] + base[200:200 + b - ov]
+        elif kind == 1:    # db suffix over query prefix
+            ov = rng.randint(1, min(a, b))
+            x = base[:b]
+            q, d = x[b - ov:] + base[200:200 + a - ov], x
+        elif kind == 2:    # the shorter inside the longer
+            lo, hi = min(a, b), max(a, b)
+            at = rng.randint(0, hi - lo)
+            q, d = base[at:at + lo], base[:hi]
+            if rng.random() < 0.5:
+                q, d = d, q
+        elif kind == 3:    # equal lengths, the same source
+            q, d = base[:a], base[:a]
+        elif kind == 4:    # short pairs over two letters: ties
+            q, d = _rand(rng, rng.randint(1, 12), b"AC"), _rand(rng, rng.randint(1, 12), b"AC")
+        else:              # unrelated
+            q, d = base[:a], base[200:200 + b]
+        if kind < 4:
+            d = _mutated(rng, d) or d
+        pairs.append((q[:200], d[:200]))
+    # constructed: a tie between a last-column cell and a last-row cell, and
+    # the db inside the query twice, 100 columns apart (two lanes of any class)
+    pairs.append((U + b"N" * 30 + U, U + b"R" * 20 + U))
+    pairs.append((b"NN" + U + b"N" * 100 + U + b"NNN", U))
+    assert all(1 <= len(q) <= 200 and 1 <= len(d) <= 200 for q, d in pairs)
+    return pairs
+
+
+def _coverage(saln, pairs):
+    """Which of the cases the batch must contain it does contain, from the model."""
+    seen = set()
+    for scheme in SCHEMES:
+        for q, d in pairs:
+            a, info = _model(q, d, scheme)
+            if not info:
+                seen.add("empty")
+                continue
+            n, m = len(q), len(d)
+            if a.db_end == m and a.q_end < n:
+                seen.add("end on the last row")
+            if a.q_end == n and a.db_end < m:
+                seen.add("end on the last column")
+            if a.q_end == n and a.db_end == m:
+                seen.add("end in the corner")
+            if a.db_begin == 0 and a.q_begin > 0:
+                seen.add("begin on row 0")
+            if a.q_begin == 0 and a.db_begin > 0:
+                seen.add("begin on column 0")
+            if a.q_begin == 0 and a.db_begin == 0:
+                seen.add("begin at the origin")
+            seen.add("end state " + info["st"])
+            if a.cigar[0][1] == "I":
+                assert a.q_begin == 0
+                seen.add("exit through I into column 0")
+            if a.cigar[0][1] == "D":
+                assert a.db_begin == 0
+                seen.add("exit through D into row 0")
+            if [i for i in info["col_ties"] if i < m] and [j for j in info["row_ties"] if j < n]:
+                seen.add("tie of a last-column and a last-row cell")
+            if len({_lane_of(saln, n, j) for j in info["row_ties"]}) > 1:
+                seen.add("tie of last-row cells in different lanes")
+    return seen
+
+
+WANTED = {"empty", "end on the last row", "end on the last column", "end in the corner",
+          "begin on row 0", "begin on column 0", "begin at the origin", "end state M", "end state I",
+          "end state D", "exit through I into column 0", "exit through D into row 0",
+          "tie of a last-column and a last-row cell", "tie of last-row cells in different lanes"}
+
+
+@pytest.fixture(scope="module")
+def random_batch(saln):
+    pairs = _make_random_batch()
+    seen = _coverage(saln, pairs)
+    assert seen >= WANTED, sorted(WANTED - seen)
+    return pairs
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_random_dovetails_and_containments(saln, random_batch, scheme):
+    qs = [q for q, _ in random_batch]
+    ds = [d for _, d in random_batch]
+    _compare(saln, qs, ds, [(k, k) for k in range(len(qs))], scheme)
+
+
+# ------------------------------------------------------------------ 3. class edges
+EDGE_QUERIES = [159, 160, 161, 255, 256, 257, 511, 512, 513, 1023, 1024]
+EDGE_DBS = [1, 63, 64, 65, 300]
+
+
+def _suffix_db(rng, q, m, j):
+    """m rows whose suffix is the query's prefix of length j (the last m bases
+    of that prefix when it is longer than the db): the end is (m, j)."""
+    if m <= j:
+        return q[j - m:j]
+    lead = bytearray(_rand(rng, m - j))
+    lead[-1] = ord("N")      # the alignment begins where the prefix does
+    return bytes(lead) + q[:j]
+
+
+def _make_edge_batch(saln, n):
+    rng = random.Random(0xED6E + n)
+    q = _rand(rng, n)
+    K = saln.ends_free.pair_geometry(n)[1]
+    ds = []
+    for m in EDGE_DBS:
+        for j in (K - 1, K, K + 1, n // 2, n - 1, n):
+            d = _suffix_db(rng, q, m, j)
+            assert len(d) == m
+            if m >= 63:      # long enough to be the only best end
+                a, _ = _model(q, d)
+                assert (a.db_end, a.q_end) == (m, j), (n, m, j, a.record())
+            ds.append(d)
+    return q, ds
+
+
+@pytest.mark.parametrize("n", EDGE_QUERIES)
+def test_class_edges(saln, n):
+    """The last-row search across lanes and registers, and the pad mask in the
+    last lane (n is not a multiple of the class's columns per lane)."""
+    q, ds = _make_edge_batch(saln, n)
+    res, _ = _compare(saln, [q], ds, [(0, b) for b in range(len(ds))])
+    assert {int(v) for v in res["db_end"]} >= set(EDGE_DBS)
+
+
+def test_pad_columns_hold_the_largest_values(saln):
+    """A query that ends inside its last lane, against a db whose every base
+    differs from it but whose pad-side values would win unmasked: the only
+    positive candidates are in real columns."""
+    qs, ds, pairs = [], [], []
+    for n in (1, 9, 11, 150, 161, 250, 300, 505, 1000, 1017):
+        q = b"A" * n
+        for d in (b"C" * 40 + b"A", b"A" + b"C" * 40, b"A" * 70):
+            pairs.append((len(qs), len(ds)))
+            qs.append(q)
+            ds.append(d)
+    _compare(saln, qs, ds, pairs)
+    _compare(saln, qs, ds, pairs, HARSH)
+
+
+# ------------------------------------------------------------------ 4. chunked fill
+def _all_long(saln, qs, ds, plist):
+    for a, b in plist:
+        assert saln.ends_free.pair_path_long(len(qs[a]), len(ds[b]))[0] == 1, (len(qs[a]), len(ds[b]))
+
+
+def _make_chunk_batch():
+    rng = random.Random(0xC0ED)
+    qs = [_rand(rng, n) for n in (1025, 2048, 2049, 2500)]
+    ds, pairs = [], []
+    for a, q in enumerate(qs):
+        n = len(q)
+        for m in (1, 64, 200):
+            # the db's suffix on the query's columns up to 1,030: the last row, over the chunk boundary
+            d1 = _suffix_db(rng, q, m, 1030 if n > 1030 else 1020)
+            # the query's suffix on the db's prefix: the last column, in the last chunk
+            d2 = q[n - m // 2:] + b"N" + _rand(rng, m)
+            # a mutated window of the last columns: ends wherever the model says
+            d3 = _mutated(rng, q[n - m:] + _rand(rng, m))
+            for d in (d1, d2[:m], d3[:m]):
+                assert len(d) == m
+                pairs.append((a, len(ds)))
+                ds.append(d)
+    return qs, ds, pairs
+
+
+@pytest.fixture(scope="module")
+def chunk_batch():
+    return _make_chunk_batch()
+
+
+@pytest.mark.parametrize("scheme", [SCHEMES[0], HARSH])
+def test_chunk_edges(saln, chunk_batch, scheme):
+    qs, ds, pairs = chunk_batch
+    _all_long(saln, qs, ds, pairs)
+    res, _ = _compare(saln, qs, ds, pairs, scheme, long=True)
+    if scheme == SCHEMES[0]:
+        ends = [(int(r["db_end"]), int(r["q_end"])) for r in res]
+        k = pairs.index((1, 3 * 3 + 2 * 3))                  # 2,048 columns, 200 rows, d1
+        assert ends[k] == (200, 1030)
+        assert ends[k + 1] == (100, 2048)                    # d2: the last column, row m / 2
+
+
+def test_long_db_short_query(saln):
+    """100 columns against 65,001 rows: one chunk, the db read as it comes;
+    the score and the end against the linear-memory model, the words by
+    re-scoring."""
+    rng = np.random.default_rng(0xDB)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    q = acgt[rng.integers(0, 4, 100)].tobytes()
+    d = acgt[rng.integers(0, 4, 65001 - 61)].tobytes() + b"N" + q[:60]
+    assert saln.ends_free.pair_path_long(100, len(d)) == (1, 1)
+    want = model.linear_ends(q, d)
+    assert want == (300, 60, 65001)
+    res, cig = saln.ends_free_align_long_batch([q], [d], mode=OVERLAP)
+    assert tuple(int(v) for v in res[0]) == (300, 0, 0, 60, 65001 - 60, 65001, 1, 0)
+    assert cig[0] == [(60, "=")]
+    # the query's suffix on the db's prefix: the last column, in row 70
+    d = q[30:] + b"N" + acgt[rng.integers(0, 4, 65001 - 71)].tobytes()
+    assert model.linear_ends(q, d) == (350, 100, 70)
+    res, cig = saln.ends_free_align_long_batch([q], [d], mode=OVERLAP)
+    assert tuple(int(v) for v in res[0]) == (350, 0, 30, 100, 0, 70, 1, 0)
+
+
+def test_last_row_best_in_chunk_0_of_three(saln):
+    rng = random.Random(0x3C)
+    q = _rand(rng, 2100)
+    d = _suffix_db(rng, q, 120, 300)
+    assert saln.ends_free.pair_path_long(2100, 120) == (1, 3)
+    a, _ = _model(q, d)
+    assert (a.db_end, a.q_end, a.q_begin) == (120, 300, 180)
+    _compare(saln, [q], [d], [(0, 0)], long=True)
+
+
+def test_ties_between_chunks_and_borders(saln):
+    # the db inside the query twice, in chunks 0 and 1: equal last-row values, the smaller column
+    q1, d1 = b"NN" + U + b"N" * 1100 + U + b"N" * 50, U
+    a, info = _model(q1, d1)
+    assert info["row_ties"] == [16, 1130] and info["col_ties"] == []
+    assert (a.score, a.db_end, a.q_end) == (70, 14, 16)
+    # the same with the second copy in chunk 2
+    q2 = b"NN" + U + b"N" * 2100 + U + b"N" * 50
+    a, info = _model(q2, d1)
+    assert info["row_ties"] == [16, 2130] and (a.db_end, a.q_end) == (14, 16)
+    # a last-row cell (chunk 0) equal to a last-column cell (row 14): the smaller row
+    q3, d3 = U + b"N" * 1100 + U, U + b"R" * 20 + U
+    a, info = _model(q3, d3)
+    assert info["row_ties"] == [14] and info["col_ties"] == [14]
+    assert (a.score, a.db_end, a.q_end, a.q_begin, a.db_begin) == (70, 14, 1128, 1114, 0)
+    # the corner equal to an earlier last-row cell: the smaller column
+    q4, d4 = U + b"N" * 1100 + U, U
+    a, info = _model(q4, d4)
+    assert info["row_ties"] == [14, 1128] and info["col_ties"] == [14]
+    assert (a.db_end, a.q_end) == (14, 14)
+    qs, ds = [q1, q2, q3, q4], [d1, d1, d3, d4]
+    _all_long(saln, qs, ds, [(k, k) for k in range(4)])
+    _compare(saln, qs, ds, [(k, k) for k in range(4)], long=True)
+
+
+def _make_mixed_batch():
+    rng = random.Random(0x313D)
+    qs = [_rand(rng, n) for n in (150, 1025, 0, 2500, 1024, 40, 1100, 300)]
+    ds = [_mutated(rng, qs[0][60:] + _rand(rng, 80)), _mutated(rng, _rand(rng, 50) + qs[1][:200]),
+          _rand(rng, 30), _mutated(rng, qs[3][2300:] + _rand(rng, 150)),
+          _mutated(rng, _rand(rng, 100) + qs[4][:400]), b"",
+          _mutated(rng, qs[6][1000:1090]), _mutated(rng, qs[7])]
+    pairs = [(0, 0), (1, 1), (2, 2), (3, 3), (4, 4), (6, 5), (5, 5), (6, 6), (7, 7), (3, 0), (0, 3),
+             (1, 5), (4, 1)]
+    return qs, ds, pairs
+
+
+@pytest.fixture(scope="module")
+def mixed_batch():
+    return _make_mixed_batch()
+
+
+def test_mixed_batch_long_equals_class(saln, mixed_batch):
+    qs, ds, pairs = mixed_batch
+    path = [saln.ends_free.pair_path_long(len(qs[a]), len(ds[b]))[0] for a, b in pairs]
+    assert path == [0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0]
+    res, cig = _compare(saln, qs, ds, pairs, long=True)
+    assert (res["score"] > 0).sum() >= 8
+    short = [k for k, lf in enumerate(path) if not lf]
+    sres, scig = saln.ends_free_align_batch(qs, ds, [pairs[k] for k in short], mode=OVERLAP)
+    for i, k in enumerate(short):
+        assert res[k] == sres[i] and cig.words(k).tolist() == scig.words(i).tolist(), pairs[k]
+
+
+# ------------------------------------------------------------------ 5. plumbing
+def _make_plumb_batch():
+    rng = random.Random(0xB1)
+    qs = [_rand(rng, n) for n in (0, 7, 150, 161, 300, 700, 1024)]
+    ds = [_mutated(rng, qs[2][50:] + _rand(rng, 60)), _mutated(rng, _rand(rng, 90) + qs[5][:310]),
+          b"", _mutated(rng, qs[6][400:500]), _rand(rng, 5)]
+    return qs, ds
+
+
+@pytest.fixture(scope="module")
+def plumb_batch():
+    return _make_plumb_batch()
+
+
+def test_all_vs_all_order(saln, plumb_batch):
+    qs, ds = plumb_batch
+    grid, gcig = _compare(saln, qs, ds, None)                 # db outer, query inner
+    order = [(a, b) for b in range(len(ds)) for a in range(len(qs))]
+    listed = order[:]
+    random.Random(3).shuffle(listed)
+    res, cig = saln.ends_free_align_batch(qs, ds, listed, mode=OVERLAP)
+    for k, pr in enumerate(listed):
+        g = order.index(pr)
+        assert res[k] == grid[g] and cig.words(k).tolist() == gcig.words(g).tolist(), pr
+    assert (grid["score"] > 0).sum() >= 6 and (grid["score"] == 0).sum() >= 6
+
+
+def test_score_only_and_plan(saln, plumb_batch):
+    import torch
+    from sequencealigning_amd import _lib
+    qs, ds = plumb_batch
+    order = [(a, b) for b in range(len(ds)) for a in range(len(qs))]
+    for long in (False, True):
+        run = saln.ends_free_align_long_batch if long else saln.ends_free_align_batch
+        res, cig = run(qs, ds, None, mode=OVERLAP, cigar=False)
+        for k, (a, b) in enumerate(order):
+            rec, _ = _expect(qs[a], ds[b])
+            assert tuple(int(v) for v in res[k]) == _score_only(rec) and cig[k] == [], (k, a, b)
+    qb, qo = saln.pack_csr(qs)
+    db, do = saln.pack_csr(ds)
+    plan = saln.EndsFreePlan(qo, do, None, mode=OVERLAP)
+    dq = torch.from_numpy(np.concatenate([qb, np.zeros(16, np.uint8)])).cuda()
+    dd = torch.from_numpy(np.concatenate([db, np.zeros(16, np.uint8)])).cuda()
+    out = [torch.full((plan.n_pairs * 8,), 77, dtype=torch.int32, device="cuda") for _ in range(2)]
+    for o in out:
+        plan.execute(dq, dd, o)
+    torch.cuda.synchronize()
+    got = [o.cpu().numpy().view(_lib.ENDS_FREE_RESULT_DTYPE) for o in out]
+    plan.close()
+    assert (got[0] == got[1]).all() and (got[0] == res).all()
+
+
+def test_trace_budget_chunks_and_cap(saln):
+    rng = random.Random(0xC4)
+    qs = [_rand(rng, n) for n in (100, 90, 120, 300, 80, 100, 60, 110, 95)]
+    ds = [_mutated(rng, q[len(q) // 3:] + _rand(rng, 40)) for q in qs]
+    ef = saln.ends_free
+    pairs = [(k, k) for k in range(len(qs))]
+    one, ocig = _compare(saln, qs, ds, pairs)
+    assert (one["score"] > 0).all()
+    sizes = [ef.trace_bytes(len(q), len(d)) for q, d in zip(qs, ds)]
+    big = int(np.argmax(sizes))
+    second = sorted(sizes)[-2]
+    assert big == 3 and second < sizes[big] - 1 and sum(sizes) - sizes[big] > 2 * second
+    # every other pair fits a chunk of its own, so the packing makes at least 3 chunks
+    res, cig = saln.ends_free_align_batch(qs, ds, pairs, mode=OVERLAP, trace_budget=second)
+    for k in range(len(qs)):
+        if k == big:     # below this pair's codes: the score and the ends alone
+            rec, _ = _expect(qs[k], ds[k])
+            assert tuple(int(v) for v in res[k]) == _score_only(rec, TRACE_CAP) and cig[k] == []
+        else:
+            assert res[k] == one[k] and cig.words(k).tolist() == ocig.words(k).tolist()
+    # the same through the long entry point, on chunked-fill pairs
+    ql = [_rand(rng, 1100) for _ in range(4)]
+    dl = [_mutated(rng, q[900:] + _rand(rng, 60))[:200] for q in ql]
+    pl = [(k, k) for k in range(4)]
+    size = ef.trace_bytes_long(1100, 200)
+    assert all(len(d) == 200 for d in dl)
+    lone, lcig = _compare(saln, ql, dl, pl, long=True)
+    res, cig = saln.ends_free_align_long_batch(ql, dl, pl, mode=OVERLAP, trace_budget=size + 8)
+    assert (res == lone).all()
+    assert [cig.words(k).tolist() for k in range(4)] == [lcig.words(k).tolist() for k in range(4)]
+    res, cig = saln.ends_free_align_long_batch(ql, dl, pl, mode=OVERLAP, trace_budget=size - 1)
+    for k in range(4):
+        rec, _ = _expect(ql[k], dl[k])
+        assert tuple(int(v) for v in res[k]) == _score_only(rec, TRACE_CAP) and cig[k] == []
+
+
+# ------------------------------------------------------------------ 6. refusals
+def test_other_mode_values_are_still_refused(saln):
+    from sequencealigning_amd import _lib
+    ef = saln.ends_free
+    q, d = [b"ACGTACGT"], [b"ACGTTACGT"]
+    off = np.array([0, 8], np.uint64), np.array([0, 9], np.uint64)
+    for mode in (0, 3, 5, -1):
+        for fn in (lambda: ef.ends_free_align_batch(q, d, mode=mode),
+                   lambda: ef.ends_free_align_long_batch(q, d, mode=mode),
+                   lambda: ef.EndsFreePlan(off[0], off[1], mode=mode)):
+            with pytest.raises(_lib.SalnError) as e:
+                fn()
+            assert e.value.code == _lib.E_INVALID and _lib.last_error() != "", mode
+    with pytest.raises(_lib.SalnError):
+        ef.ends_free_align_batch(q, d, mode=0)
+    assert "saln_nw_" in _lib.last_error()
+
+
+def test_nw_entry_points_refuse_the_mode(saln):
+    with pytest.raises(saln.AlignmentError, match="not implemented"):
+        saln.n_w_align(b"ACGT", b"ACGT", False, OVERLAP)
+    with pytest.raises(saln.AlignmentError, match="not implemented"):
+        saln.nw_align_batch([b"ACGT"], [b"ACGT"], [(0, 0)], OVERLAP)
