@@ -1,11 +1,14 @@
 // Ends-free engine (include/saln.h, saln_ends_free_*): what the host file
-// (ends_free_host.cpp) and the kernels (ends_free_kernels.hip) share.  The
-// device-side helpers of the fill and the walk are in ends_free_dev.hpp.
+// (ends_free_host.cpp) and the kernels (ends_free_kernels.hip,
+// ends_free_long_kernels.hip) share.  Device side: ends_free_dev.hpp has what
+// the fills and the walk share (the trace code), ends_free_fill.hpp the fill
+// itself, which both fill kernels are built from.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "saln.h"
 
@@ -23,6 +26,19 @@ static_assert(sizeof(EfPair) == 48, "EfPair layout");
 struct EfScoring {
     int32_t match, mismatch, open, extend;
 };
+
+// The run-time mode as a compile-time constant: f(std::integral_constant<int,
+// SALN_MODE_...>{}) for the engine's three modes, hipErrorInvalidValue for
+// anything else.  Every kernel template's instances are picked through it.
+template <class F>
+hipError_t ef_with_mode(int32_t mode, F &&f) {
+    switch (mode) {
+        case SALN_MODE_LOCAL: return f(std::integral_constant<int, SALN_MODE_LOCAL>{});
+        case SALN_MODE_OVERLAP: return f(std::integral_constant<int, SALN_MODE_OVERLAP>{});
+        case SALN_MODE_SEMI_GLOBAL: return f(std::integral_constant<int, SALN_MODE_SEMI_GLOBAL>{});
+        default: return hipErrorInvalidValue;
+    }
+}
 
 // Query classes: one pair per group of `lanes` lanes, `cols` query columns per
 // lane, the whole query in one chunk (the i32 lane classes of the NW table).

@@ -1,5 +1,7 @@
-// Device helpers shared by the fill and the walk of the ends-free engine
-// (ends_free_kernels.hip): the 4-bit trace code of a cell and where it lives.
+// Device helpers shared by the fills and the walk of the ends-free engine:
+// the 4-bit trace code of a cell and where it lives, -infinity and its
+// arithmetic, the lane hand-over.  The fill's own steps (row 0, a row, the end
+// cell) are in ends_free_fill.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,228 @@
+// The steps of the ends-free fill: row 0, a lane's row of K cells (the Gotoh
+// recurrence, the trace code, the three modes' end-cell trackers), the code
+// store, overlap's last row, and the group's end cell with its record.
+// ef_fill_kernel (ends_free_kernels.hip) is built from all of them.
+// ef_fill_long_kernel (ends_free_long_kernels.hip) uses those outside its
+// loops (ef_overlap_end, ef_reduce_best, ef_store_end) and keeps its own row 0,
+// row and chunk code: built from ef_row0 / ef_row its step loop compiled to
+// other code and measured 0.5-1.5 % slower, so a change
+// to the recurrence, the codes or the trackers here is made there too.
+//
+// A lane holds K consecutive query columns col0+1 .. col0+K (col0 absolute) in
+// registers: qc their bases, Hp = P(r-1, j), Dn = D(r, j).  kMode is
+// SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
+#pragma once
+#include "ends_free_dev.hpp"
+
+namespace saln {
+
+// The best end cell of a lane's columns over the rows it has run, rows rising:
+//   local        every M(i, j), strictly positive; k is the register of the
+//                column (col0 + k + 1), the smallest row, then column, kept
+//   semi-global  max(M, I)(i, lq) in the lane that holds column lq, row 0
+//                first; k is the end state (0 M, 1 I)
+//   overlap      P(i, lq) in that lane, strictly positive (the last row's
+//                candidates: ef_last_row_best)
+struct EfBest {
+    int32_t v;
+    uint32_t i, k;
+};
+
+template <int kMode>
+__device__ __forceinline__ EfBest ef_best_row0(uint32_t lq, int32_t o, int32_t e) {
+    if constexpr (kMode == SALN_MODE_SEMI_GLOBAL)
+        return {o + (int32_t)lq * e, 0u, 1u};  // row 0 ends in I
+    else
+        return {0, 0u, 0u};
+}
+
+// Row 0 of the columns behind col0.  Returns hd = P(0, col0).
+template <int K, int kMode>
+__device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32_t lq, uint32_t col0,
+                                           int32_t o, int32_t e, uint32_t (&qc)[K], int32_t (&Hp)[K],
+                                           int32_t (&Dn)[K]) {
+    constexpr bool kSemi = kMode == SALN_MODE_SEMI_GLOBAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const uint32_t j = col0 + k + 1;
+        qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
+        // semi-global P(0, j) = I(0, j) = o + j e; local and overlap P = 0
+        Hp[k] = !kSemi ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
+        // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
+        Dn[k] = kOverlap ? o + e : kEfNeg;
+    }
+    return !kSemi || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
+}
+
+// A lane's K codes of one row (4 bits per cell), column col0 + 1 in the low
+// nibble of w[0].
+template <int K>
+struct EfCodes {
+    static_assert(K % 2 == 0, "two cells per code byte");
+    uint32_t w[(K + 7) / 8];
+};
+
+// Stores those K / 2 bytes at `to`.  A pair's codes start 8-byte aligned and a
+// row is a whole number of lanes' parts, so a part of 8 (K = 16) or 4 (K = 8)
+// bytes is aligned and goes out as one store; other parts go out by bytes.
+template <int K>
+__device__ __forceinline__ void ef_store_codes(uint8_t *to, const EfCodes<K> &c) {
+    if constexpr (K % 16 == 0) {
+#pragma unroll
+        for (int n = 0; n < K / 16; ++n) reinterpret_cast<uint2 *>(to)[n] = make_uint2(c.w[2 * n], c.w[2 * n + 1]);
+    } else if constexpr (K % 8 == 0) {
+#pragma unroll
+        for (int n = 0; n < K / 8; ++n) reinterpret_cast<uint32_t *>(to)[n] = c.w[n];
+    } else {
+#pragma unroll
+        for (int n = 0; n < K / 2; ++n) to[n] = (uint8_t)(c.w[n / 4] >> (8 * (n % 4)));
+    }
+}
+
+// Row r (1 <= r <= ld) of the lane's columns.  dch = d[r-1]; inF = I(r, col0+1)
+// and inH = P(r, col0) come from the left neighbour or the boundary.  Leaves
+// hd = P(r, col0) for row r + 1 and pubF = I(r, col0+K+1), pubH = P(r, col0+K)
+// for the right neighbour, updates the lane's best end cell, and with kCodes
+// leaves the cells' codes in `codes`.  k_end: the register of column lq in its
+// lane.
+template <int K, int kMode, bool kCodes>
+__device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, int32_t inF, int32_t inH,
+                                       const EfScoring &sc, uint32_t k_end, uint32_t r,
+                                       int32_t (&Hp)[K], int32_t (&Dn)[K], int32_t &hd, int32_t &pubF,
+                                       int32_t &pubH, EfBest &best, EfCodes<K> &codes) {
+    constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    const int32_t o = sc.open, e = sc.extend;
+    int32_t F = inF;
+    int32_t Msel = kEfNeg, Isel = kEfNeg;
+    if constexpr (kCodes) {
+#pragma unroll
+        for (int n = 0; n < (K + 7) / 8; ++n) codes.w[n] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int32_t M = ef_add(hd, qc[k] == dch ? sc.match : sc.mismatch);
+        const int32_t I = F, D = Dn[k];
+        const int32_t P3 = max(M, max(I, D));
+        const int32_t P = kLocal ? max(P3, 0) : P3;
+        const int32_t tO = ef_add(M, o);
+        if constexpr (kCodes) {
+            uint32_t c = M == P3 ? 0u : I == P3 ? 1u : 2u;
+            if constexpr (kLocal) c = P3 <= 0 ? kEfStop : c;
+            c |= I >= tO ? kEfIExt : 0u;
+            c |= D >= tO ? kEfDExt : 0u;
+            codes.w[k / 8] |= c << (4 * (k % 8));
+        }
+        if constexpr (kLocal) {
+            // rows and columns come in increasing order: > keeps the
+            // smallest row, then the smallest column, of my columns
+            const bool b = M > best.v;
+            best.v = b ? M : best.v;
+            best.i = b ? r : best.i;
+            best.k = b ? (uint32_t)k : best.k;
+        } else if constexpr (kOverlap) {
+            Msel = (uint32_t)k == k_end ? P3 : Msel;  // P(r, my k_end-th column)
+        } else {
+            Msel = (uint32_t)k == k_end ? M : Msel;
+            Isel = (uint32_t)k == k_end ? I : Isel;
+        }
+        F = ef_add(max(tO, I), e);      // I(r, j+1)
+        Dn[k] = ef_add(max(tO, D), e);  // D(r+1, j)
+        hd = Hp[k];
+        Hp[k] = P;
+    }
+    hd = inH;
+    pubF = F;
+    pubH = Hp[K - 1];
+    if constexpr (kOverlap) {
+        const bool b = Msel > best.v;  // the smallest row wins a tie
+        best.v = b ? Msel : best.v;
+        best.i = b ? r : best.i;
+    } else if constexpr (!kLocal) {
+        const int32_t v = max(Msel, Isel);
+        const bool b = v > best.v;  // the smallest row wins a tie
+        best.v = b ? v : best.v;
+        best.i = b ? r : best.i;
+        best.k = b ? (Msel >= Isel ? 0u : 1u) : best.k;  // M before I
+    }
+}
+
+// Overlap's last row: Hp holds P(ld, j) of the lane's columns (row 0's zeros
+// when ld == 0).  Pad columns hold real-looking values and are masked out.
+// Strict > over rising columns keeps the smallest column in
+// (rbest, rbest_j), rbest_j absolute; they start from (0, 0).
+template <int K>
+__device__ __forceinline__ void ef_last_row_best(const int32_t (&Hp)[K], uint32_t col0, uint32_t lq,
+                                                 int32_t &rbest, uint32_t &rbest_j) {
+    // Keep the register index of the new best (plus 1; 0: none) and add col0
+    // once at the end: selecting the columns themselves makes the compiler
+    // hold all K of them live over the row loop, which costs the K = 16
+    // class fill with codes a wave per SIMD.
+    uint32_t k1 = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const bool b = col0 + (uint32_t)k + 1 <= lq && Hp[k] > rbest;
+        rbest = b ? Hp[k] : rbest;
+        k1 = b ? (uint32_t)k + 1 : k1;
+    }
+    rbest_j = k1 ? col0 + k1 : rbest_j;
+}
+
+// Overlap's end cell of a lane: its last-column cell (v, i), which only the
+// owner of column lq tracked, against its last-row cell.  A last-column cell
+// above row ld wins a tie; in row ld it is the corner, and the last row's
+// smallest column wins.
+__device__ __forceinline__ void ef_overlap_end(bool owner, uint32_t lq, uint32_t ld, int32_t rbest,
+                                               uint32_t rbest_j, int32_t &v, uint32_t &i, uint32_t &j) {
+    if (!owner) v = 0;
+    const bool row = rbest > v || (rbest == v && i == ld);
+    v = row ? rbest : v;
+    i = row ? ld : i;
+    j = row ? rbest_j : lq;
+}
+
+// The pair's record: score and end cell; the walk fills in the rest.
+template <bool kCodes>
+__device__ __forceinline__ void ef_store_end(saln_ends_free_result *__restrict__ results,
+                                             uint8_t *__restrict__ end_state, uint32_t out, int32_t score,
+                                             uint32_t db_end, uint32_t q_end, uint32_t state) {
+    saln_ends_free_result res;
+    res.score = score;
+    res.status = SALN_OK;
+    res.q_begin = res.db_begin = -1;
+    res.q_end = (int32_t)q_end;
+    res.db_end = (int32_t)db_end;
+    res.cigar_len = res.reserved = 0;
+    results[out] = res;
+    if constexpr (kCodes) end_state[out] = (uint8_t)state;
+}
+
+// The group's end cell from its lanes' (v, row i, absolute column j), and the
+// record.  Local and overlap: the largest value, then the smallest row, then
+// the smallest column (lanes met a row at different steps: the row index
+// decides, not the step); lanes without a positive cell lose to every real
+// cell, and a pair without one ends at the origin with score 0.  Semi-global:
+// the owner of column lq holds it, with its end state.
+template <int G, int kMode, bool kCodes>
+__device__ __forceinline__ void ef_reduce_best(int lane, bool owner, int32_t v, uint32_t i, uint32_t j,
+                                               uint32_t state, uint32_t lq,
+                                               saln_ends_free_result *__restrict__ results,
+                                               uint8_t *__restrict__ end_state, uint32_t out) {
+    if constexpr (kMode == SALN_MODE_SEMI_GLOBAL) {
+        if (owner) ef_store_end<kCodes>(results, end_state, out, v, i, lq, state);
+    } else {
+        if (v <= 0) i = 0xFFFFFFFFu;
+#pragma unroll
+        for (int off = G / 2; off >= 1; off >>= 1) {
+            const int32_t ov = __shfl_xor(v, off, G);
+            const uint32_t oi = __shfl_xor(i, off, G);
+            const uint32_t oj = __shfl_xor(j, off, G);
+            const bool take = ov > v || (ov == v && (oi < i || (oi == i && oj < j)));
+            v = take ? ov : v;
+            i = take ? oi : i;
+            j = take ? oj : j;
+        }
+        if (lane == 0) ef_store_end<kCodes>(results, end_state, out, v, v > 0 ? i : 0u, v > 0 ? j : 0u, 0u);
+    }
+}
+
+}  // namespace saln

@@ -9,25 +9,21 @@
 // lanes, K query columns per lane in registers, the rows skewed over the
 // lanes (lane l works on row t - l + 1 at step t), the left neighbour's
 // boundary (P and the I candidate leaving its last column) handed over by
-// DPP, the group's db row staged in LDS.  Values are plain int32.  Each lane
-// keeps the best end cell of its own columns; the group reduces them at the
-// end on (value, row, column), never on the step.
+// DPP.  Values are plain int32.  Each lane keeps the best end cell of its own
+// columns; the group reduces them at the end on (value, row, column), never
+// on the step.  Row 0, a lane's row, the code store and the end cell are those
+// of ends_free_fill.hpp (the chunked fill shares the end cell and keeps a row
+// of its own); this kernel adds the group's db row staged in LDS, constants on
+// lane 0's boundary (column 0) and the one pass over the rows.
 //
 // Walk: one pair per lane, from the reported end cell along the 4-bit codes.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "ends_free_dev.hpp"
+#include "ends_free_fill.hpp"
 
 namespace saln {
-
-// A lane's K / 2 code bytes of one row.  A pair's codes start 8-byte aligned
-// and a row is a whole number of these, so 4- and 8-byte rows are aligned.
-template <int K>
-struct __attribute__((packed, aligned((K / 2) % 8 == 0 ? 8 : (K / 2) % 4 == 0 ? 4 : 1))) EfCodeRow {
-    uint8_t b[K / 2];
-};
 
 // kMode: SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
 template <int G, int K, int kMode, bool kCodes>
@@ -36,7 +32,6 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
     uint32_t ld_max) {
-    static_assert(K % 2 == 0, "two cells per code byte");
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     const int gpb = (int)blockDim.x / G;
     const int lane = (int)threadIdx.x % G, grp = (int)threadIdx.x / G;
@@ -44,18 +39,9 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     if (gi >= count) return;  // whole group (DPP never crosses groups)
     const EfPair p = pairs[first + gi];
     const uint32_t lq = p.lq, ld = p.ld;
-    const uint8_t *__restrict__ q = qs + p.q_off;
     const uint8_t *__restrict__ d = ds + p.d_off;
-    saln_ends_free_result res;
-    res.status = SALN_OK;
-    res.q_begin = res.db_begin = -1;
-    res.cigar_len = res.reserved = 0;
     if (lq == 0) {  // no column: score 0 at the origin in every mode
-        if (lane == 0) {
-            res.score = res.q_end = res.db_end = 0;
-            results[p.out] = res;
-            if constexpr (kCodes) end_state[p.out] = 0;
-        }
+        if (lane == 0) ef_store_end<kCodes>(results, end_state, p.out, 0, 0u, 0u, 0u);
         return;
     }
     extern __shared__ uint8_t ef_drow[];  // [groups][G + ld_max + G] db bytes
@@ -70,29 +56,14 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     const uint32_t jend = lq - 1;
     const uint32_t l_end = jend / K, k_end = jend % K;  // the lane and register of column lq
     uint32_t qc[K];
-    int32_t Hp[K], Dn[K];  // P(r-1, j) and D(r, j) of my columns
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const uint32_t j = col0 + k + 1;
-        qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
-        // row 0: semi-global P(0, j) = I(0, j) = o + j e; local and overlap P = 0
-        Hp[k] = kLocal || kOverlap ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
-        // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
-        Dn[k] = kOverlap ? o + e : kEfNeg;
-    }
-    int32_t hd = kLocal || kOverlap || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;  // P(0, col0)
+    int32_t Hp[K], Dn[K];
+    int32_t hd = ef_row0<K, kMode>(qs + p.q_off, lq, col0, o, e, qc, Hp, Dn);
     // column 0, entering lane 0: P(i, 0) = 0 in every mode (the free start of
     // semi-global and overlap, local's floor); I(i, 1) opens from M(i, 0) = 0
     // in semi-global and overlap and is -inf in local
     const int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
     int32_t pubF = kEfNeg, pubH = kEfNeg;
-    // best end cell of my columns: local every M(i, j), strictly positive;
-    // semi-global max(M, I)(i, lq) in the lane holding column lq, row 0 first;
-    // overlap P(i, lq) in that lane, strictly positive (the last row's
-    // candidates are taken from Hp after the loop)
-    int32_t best = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
-    uint32_t best_i = 0, best_k = 0;  // semi-global: best_k is the end state
-    if (!kLocal && !kOverlap) best_k = 1;  // row 0 ends in I
+    EfBest best = ef_best_row0<kMode>(lq, o, e);
     uint8_t *crow = nullptr;
     if constexpr (kCodes) crow = codes + p.code_off + (size_t)lane * (K / 2);
     const int T = (int)ld + G - 1;
@@ -102,115 +73,23 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
         const int32_t inF = ef_shr1<G>(bF, pubF);  // I(r, col0+1)
         const int32_t inH = ef_shr1<G>(bH, pubH);  // P(r, col0)
         if (r >= 1 && r <= (int)ld) {
-            int32_t F = inF;
-            int32_t Msel = kEfNeg, Isel = kEfNeg;
-            uint32_t nib[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int32_t M = ef_add(hd, qc[k] == dch ? sc.match : sc.mismatch);
-                const int32_t I = F, D = Dn[k];
-                const int32_t P3 = max(M, max(I, D));
-                const int32_t P = kLocal ? max(P3, 0) : P3;
-                const int32_t tO = ef_add(M, o);
-                if constexpr (kCodes) {
-                    uint32_t c = M == P3 ? 0u : I == P3 ? 1u : 2u;
-                    if constexpr (kLocal) c = P3 <= 0 ? kEfStop : c;
-                    c |= I >= tO ? kEfIExt : 0u;
-                    c |= D >= tO ? kEfDExt : 0u;
-                    nib[k] = c;
-                }
-                if constexpr (kLocal) {
-                    // rows and columns come in increasing order: > keeps the
-                    // smallest row, then the smallest column, of my columns
-                    const bool b = M > best;
-                    best = b ? M : best;
-                    best_i = b ? (uint32_t)r : best_i;
-                    best_k = b ? (uint32_t)k : best_k;
-                } else if constexpr (kOverlap) {
-                    Msel = (uint32_t)k == k_end ? P3 : Msel;  // P(r, my k_end-th column)
-                } else {
-                    Msel = (uint32_t)k == k_end ? M : Msel;
-                    Isel = (uint32_t)k == k_end ? I : Isel;
-                }
-                F = ef_add(max(tO, I), e);      // I(r, j+1)
-                Dn[k] = ef_add(max(tO, D), e);  // D(r+1, j)
-                hd = Hp[k];
-                Hp[k] = P;
-            }
-            hd = inH;
-            pubF = F;
-            pubH = Hp[K - 1];
-            if constexpr (kOverlap) {
-                const bool b = Msel > best;  // the smallest row wins a tie
-                best = b ? Msel : best;
-                best_i = b ? (uint32_t)r : best_i;
-            } else if constexpr (!kLocal) {
-                const int32_t v = max(Msel, Isel);
-                const bool b = v > best;  // the smallest row wins a tie
-                best = b ? v : best;
-                best_i = b ? (uint32_t)r : best_i;
-                best_k = b ? (Msel >= Isel ? 0u : 1u) : best_k;  // M before I
-            }
+            EfCodes<K> row;
+            ef_row<K, kMode, kCodes>(qc, dch, inF, inH, sc, k_end, (uint32_t)r, Hp, Dn, hd, pubF, pubH, best, row);
             if constexpr (kCodes) {
-                if (col0 < lq) {  // lanes wholly past the query store nothing
-                    EfCodeRow<K> w;
-#pragma unroll
-                    for (int k = 0; k < K; k += 2) w.b[k / 2] = (uint8_t)(nib[k] | (nib[k + 1] << 4));
-                    *reinterpret_cast<EfCodeRow<K> *>(crow + (size_t)(r - 1) * p.row_bytes) = w;
-                }
+                // lanes wholly past the query store nothing
+                if (col0 < lq) ef_store_codes<K>(crow + (size_t)(r - 1) * p.row_bytes, row);
             }
         }
     }
+    uint32_t best_j = col0 + best.k + 1;  // local's column
     if constexpr (kOverlap) {
-        // Only the lane of column lq tracked a last-column cell.  The last
-        // row: Hp holds P(ld, j) of my columns (row 0's zeros when ld == 0).
-        // Strict > from 0 over rising columns keeps the smallest column; pad
-        // columns hold real-looking values and are masked out.
-        if ((uint32_t)lane != l_end) best = 0;
-        best_k = k_end;
         int32_t rbest = 0;
-        uint32_t rbest_k = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const bool b = col0 + (uint32_t)k + 1 <= lq && Hp[k] > rbest;
-            rbest = b ? Hp[k] : rbest;
-            rbest_k = b ? (uint32_t)k : rbest_k;
-        }
-        // a last-column cell above row ld wins a tie with a last-row cell; in
-        // row ld it is the corner, and the last row's smallest column wins
-        const bool row = rbest > best || (rbest == best && best_i == ld);
-        best = row ? rbest : best;
-        best_i = row ? ld : best_i;
-        best_k = row ? rbest_k : best_k;
+        uint32_t rbest_j = 0;
+        ef_last_row_best<K>(Hp, col0, lq, rbest, rbest_j);
+        ef_overlap_end((uint32_t)lane == l_end, lq, ld, rbest, rbest_j, best.v, best.i, best_j);
     }
-    if constexpr (kLocal || kOverlap) {
-        // the group's best: the largest value, then the smallest row, then
-        // the smallest column (lanes met a row at different steps: the row
-        // index decides, not the step).  Lanes without a positive cell hold
-        // (0, row 0, column col0+1) and lose to every real cell.
-        uint32_t ij = best > 0 ? (best_i << 11) | (col0 + best_k + 1) : 0xFFFFFFFFu;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-            const int32_t ov = __shfl_xor(best, off, G);
-            const uint32_t oij = __shfl_xor(ij, off, G);
-            const bool take = ov > best || (ov == best && oij < ij);
-            best = take ? ov : best;
-            ij = take ? oij : ij;
-        }
-        if (lane == 0) {
-            res.score = best;
-            res.db_end = best > 0 ? (int32_t)(ij >> 11) : 0;
-            res.q_end = best > 0 ? (int32_t)(ij & 2047u) : 0;
-            results[p.out] = res;
-            if constexpr (kCodes) end_state[p.out] = 0;
-        }
-    } else if ((uint32_t)lane == l_end) {
-        res.score = best;
-        res.db_end = (int32_t)best_i;
-        res.q_end = (int32_t)lq;
-        results[p.out] = res;
-        if constexpr (kCodes) end_state[p.out] = (uint8_t)best_k;
-    }
+    ef_reduce_best<G, kMode, kCodes>(lane, (uint32_t)lane == l_end, best.v, best.i, best_j, best.k, lq,
+                                     results, end_state, p.out);
 }
 
 // One pair per lane.  Words are written back to front so that they end at
@@ -250,37 +129,24 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
         if (i > 0 && j > 0) st = ef_code(codes, p, i, j) & kEfArgMask;
     }
     while (j > 0) {
-        if constexpr (kOverlap) {
-            // every cell of row 0 and column 0 is a free start: the walk ends
-            // as soon as it stands on one, in M or after a gap that opened there
-            if (i == 0) break;
-            if (st == 0) {
-                emit(q[j - 1] == d[i - 1] ? SALN_CIGAR_EQ : SALN_CIGAR_X, 1);
-                --i, --j;
-                if (i == 0 || j == 0) break;
-                st = ef_code(codes, p, i, j) & kEfArgMask;
-            } else if (st == 1) {
-                emit(SALN_CIGAR_I, 1);
-                --j;  // column 0: I(i, 1) opened from M(i, 0)
-                st = j > 0 && (ef_code(codes, p, i, j) & kEfIExt) ? 1u : 0u;
-            } else {
-                emit(SALN_CIGAR_D, 1);
-                --i;  // row 0: D(1, j) opened from M(0, j)
-                st = i > 0 && (ef_code(codes, p, i, j) & kEfDExt) ? 2u : 0u;
+        if (i == 0) {
+            // row 0.  Overlap: a free start, in M or after a D run that opened
+            // there.  Semi-global: the rest of the query is one insertion.
+            // (Local never stands here: its D(1, j) is -inf.)
+            if constexpr (!kOverlap) {
+                if (!kLocal) emit(SALN_CIGAR_I, j);
+                j = 0;
             }
-            continue;
-        }
-        if (i == 0) {  // semi-global row 0: the rest of the query is one insertion
-            if (!kLocal) emit(SALN_CIGAR_I, j);
-            j = 0;
             break;
         }
         if (st == 0) {
             emit(q[j - 1] == d[i - 1] ? SALN_CIGAR_EQ : SALN_CIGAR_X, 1);
             --i, --j;
             if (i == 0 || j == 0) {
-                if (kLocal) break;  // P = 0 on the border: the alignment begins here
-                st = 1;             // semi-global row 0 is I; column 0 ends the loop
+                // local: P = 0 on the border, the alignment begins here;
+                // overlap: every cell of row 0 and column 0 is a free start
+                if (kLocal || kOverlap) break;
+                st = 1;  // semi-global row 0 is I; column 0 ends the loop
                 continue;
             }
             const uint32_t a = ef_code(codes, p, i, j) & kEfArgMask;
@@ -294,7 +160,8 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
         } else {
             emit(SALN_CIGAR_D, 1);
             --i;
-            // (D(1, j) is -inf: a D run never reaches row 0)
+            // row 0: overlap's D(1, j) opens from M(0, j); elsewhere it is
+            // -inf and a D run never reaches row 0
             st = i > 0 && (ef_code(codes, p, i, j) & kEfDExt) ? 2u : 0u;
         }
     }
@@ -322,21 +189,32 @@ __global__ __launch_bounds__(256) void ef_gather_kernel(
 
 namespace {
 
+// What every class's launch takes.
+struct FillLaunch {
+    int32_t mode;
+    dim3 grid, block;
+    size_t lds;
+    hipStream_t s;
+    const EfPair *pairs;
+    uint32_t first, count;
+    const uint8_t *qs, *ds;
+    uint8_t *codes, *end_state;
+    saln_ends_free_result *results;
+    EfScoring sc;
+    uint32_t ld_max;
+};
+
 template <int G, int K>
-hipError_t fill_class(int32_t mode, bool with_codes, dim3 grid, dim3 block, size_t lds, hipStream_t s,
-                      const EfPair *pairs, uint32_t first, uint32_t count, const uint8_t *qs,
-                      const uint8_t *ds, uint8_t *codes, uint8_t *end_state,
-                      saln_ends_free_result *results, EfScoring sc, uint32_t ld_max) {
+hipError_t fill_class(const FillLaunch &a) {
     auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state,
-                           results, sc, ld_max);
+        hipLaunchKernelGGL(kernel, a.grid, a.block, a.lds, a.s, a.pairs, a.first, a.count, a.qs, a.ds,
+                           a.codes, a.end_state, a.results, a.sc, a.ld_max);
         return hipGetLastError();
     };
-    constexpr int kL = SALN_MODE_LOCAL, kS = SALN_MODE_SEMI_GLOBAL, kO = SALN_MODE_OVERLAP;
-    if (mode == kL) return with_codes ? go(ef_fill_kernel<G, K, kL, true>) : go(ef_fill_kernel<G, K, kL, false>);
-    if (mode == kO) return with_codes ? go(ef_fill_kernel<G, K, kO, true>) : go(ef_fill_kernel<G, K, kO, false>);
-    if (mode != kS) return hipErrorInvalidValue;
-    return with_codes ? go(ef_fill_kernel<G, K, kS, true>) : go(ef_fill_kernel<G, K, kS, false>);
+    return ef_with_mode(a.mode, [&](auto m) {
+        constexpr int kMode = decltype(m)::value;
+        return a.codes ? go(ef_fill_kernel<G, K, kMode, true>) : go(ef_fill_kernel<G, K, kMode, false>);
+    });
 }
 
 }  // namespace
@@ -352,13 +230,13 @@ hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t f
     uint32_t groups = 256u / G;
     while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > (64u << 10)) --groups;
     const size_t lds = (size_t)ef_lds_bytes(cls, groups, ld_max);
-    const dim3 grid((count + groups - 1) / groups), block(groups * G);
-    const bool wc = codes != nullptr;
+    const FillLaunch a{mode, dim3((count + groups - 1) / groups), dim3(groups * G), lds, s, pairs, first, count,
+                       qs, ds, codes, end_state, results, sc, ld_max};
     switch (cls) {
-        case 0: return fill_class<16, 10>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        case 1: return fill_class<16, 16>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        case 2: return fill_class<64, 8>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
-        default: return fill_class<64, 16>(mode, wc, grid, block, lds, s, pairs, first, count, qs, ds, codes, end_state, results, sc, ld_max);
+        case 0: return fill_class<16, 10>(a);
+        case 1: return fill_class<16, 16>(a);
+        case 2: return fill_class<64, 8>(a);
+        default: return fill_class<64, 16>(a);
     }
 }
 
@@ -368,18 +246,11 @@ hipError_t launch_ef_walk(int32_t mode, const EfPair *pairs, uint32_t count, con
                           hipStream_t s) {
     if (count == 0) return hipSuccess;
     const dim3 grid((count + 63) / 64), block(64);
-    if (mode == SALN_MODE_LOCAL)
-        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_LOCAL>, grid, block, 0, s, pairs, count, qs, ds,
+    return ef_with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(ef_walk_kernel<decltype(m)::value>, grid, block, 0, s, pairs, count, qs, ds,
                            codes, end_state, results, words, lens);
-    else if (mode == SALN_MODE_OVERLAP)
-        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_OVERLAP>, grid, block, 0, s, pairs, count, qs, ds,
-                           codes, end_state, results, words, lens);
-    else if (mode == SALN_MODE_SEMI_GLOBAL)
-        hipLaunchKernelGGL(ef_walk_kernel<SALN_MODE_SEMI_GLOBAL>, grid, block, 0, s, pairs, count, qs,
-                           ds, codes, end_state, results, words, lens);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_ef_gather(const EfPair *pairs, uint32_t count, const uint32_t *words,

@@ -18,17 +18,20 @@
 //    register loaded 64 steps ahead;
 //  - local's best cell: a best per chunk on strict > (rows rise inside a
 //    chunk), merged into the running best on (value, row) at the chunk's end,
-//    and a final reduction over the lanes on (value, row, column) in full
-//    32-bit words;
+//    before the reduction over the lanes;
 //  - overlap's end cell: the owner of column n (in the last chunk) keeps the
 //    best P(r, n) as semi-global's does; every lane takes the last row's
 //    candidates from Hp after each chunk's last row, merged on strict > so
 //    that an earlier chunk keeps the smaller column; then local's reduction.
+// The owner's merge, the reduction and the record are ends_free_fill.hpp's.
+// Row 0, the row and the trackers are written out here and equal ef_row0 and
+// ef_row: built from those, this kernel's step loop compiled to other code and
+// measured 0.5-1.5 % slower.  Keep them equal.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "ends_free_dev.hpp"
+#include "ends_free_fill.hpp"
 
 namespace saln {
 
@@ -69,16 +72,8 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         const uint32_t lq = p.lq, ld = p.ld;
         const uint8_t *__restrict__ q = qs + p.q_off;
         const uint8_t *__restrict__ d = ds + p.d_off;
-        saln_ends_free_result res;
-        res.status = SALN_OK;
-        res.q_begin = res.db_begin = -1;
-        res.cigar_len = res.reserved = 0;
         if (lq == 0) {  // no column: score 0 at the origin in every mode
-            if (lane == 0) {
-                res.score = res.q_end = res.db_end = 0;
-                results[p.out] = res;
-                if constexpr (kCodes) end_state[p.out] = 0;
-            }
+            if (lane == 0) ef_store_end<kCodes>(results, end_state, p.out, 0, 0u, 0u, 0u);
             continue;
         }
         const uint32_t nchunks = (lq + kEfChunkCols - 1) / (uint32_t)kEfChunkCols;
@@ -239,45 +234,10 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                 best_st = cbest_k;
             }
         }
-        if constexpr (kOverlap) {
-            // only the lane of column lq (of the last chunk) tracked it.  A
-            // last-column cell above row ld wins a tie with a last-row cell;
-            // in row ld it is the corner, and the last row's smallest column wins
-            if ((uint32_t)lane != l_end) best = 0;
-            best_j = lq;
-            const bool row = rbest > best || (rbest == best && best_i == ld);
-            best = row ? rbest : best;
-            best_i = row ? ld : best_i;
-            best_j = row ? rbest_j : best_j;
-        }
-        if constexpr (kLocal || kOverlap) {
-            // the wave's best: the largest value, then the smallest row, then
-            // the smallest column.  Lanes without a positive cell lose.
-            uint32_t bi = best > 0 ? best_i : 0xFFFFFFFFu, bj = best_j;
-#pragma unroll
-            for (int off = kLanes / 2; off >= 1; off >>= 1) {
-                const int32_t ov = __shfl_xor(best, off, kLanes);
-                const uint32_t oi = __shfl_xor(bi, off, kLanes);
-                const uint32_t oj = __shfl_xor(bj, off, kLanes);
-                const bool take = ov > best || (ov == best && (oi < bi || (oi == bi && oj < bj)));
-                best = take ? ov : best;
-                bi = take ? oi : bi;
-                bj = take ? oj : bj;
-            }
-            if (lane == 0) {
-                res.score = best;
-                res.db_end = best > 0 ? (int32_t)bi : 0;
-                res.q_end = best > 0 ? (int32_t)bj : 0;
-                results[p.out] = res;
-                if constexpr (kCodes) end_state[p.out] = 0;
-            }
-        } else if ((uint32_t)lane == l_end) {
-            res.score = best;
-            res.db_end = (int32_t)best_i;
-            res.q_end = (int32_t)lq;
-            results[p.out] = res;
-            if constexpr (kCodes) end_state[p.out] = (uint8_t)best_st;
-        }
+        const bool owner = (uint32_t)lane == l_end;  // of column lq, in the last chunk
+        if constexpr (kOverlap) ef_overlap_end(owner, lq, ld, rbest, rbest_j, best, best_i, best_j);
+        ef_reduce_best<kLanes, kMode, kCodes>(lane, owner, best, best_i, best_j, best_st, lq, results, end_state,
+                                              p.out);
         // the next pair reuses the boundary column and the ring
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     }
@@ -294,11 +254,10 @@ hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first
                            end_state, results, sc, static_cast<int2 *>(bnd), slot_rows, counter);
         return hipGetLastError();
     };
-    constexpr int kL = SALN_MODE_LOCAL, kS = SALN_MODE_SEMI_GLOBAL, kO = SALN_MODE_OVERLAP;
-    if (mode == kL) return codes ? go(ef_fill_long_kernel<kL, true>) : go(ef_fill_long_kernel<kL, false>);
-    if (mode == kO) return codes ? go(ef_fill_long_kernel<kO, true>) : go(ef_fill_long_kernel<kO, false>);
-    if (mode != kS) return hipErrorInvalidValue;
-    return codes ? go(ef_fill_long_kernel<kS, true>) : go(ef_fill_long_kernel<kS, false>);
+    return ef_with_mode(mode, [&](auto m) {
+        constexpr int kMode = decltype(m)::value;
+        return codes ? go(ef_fill_long_kernel<kMode, true>) : go(ef_fill_long_kernel<kMode, false>);
+    });
 }
 
 }  // namespace saln
