@@ -50,7 +50,9 @@ typedef enum {
     SALN_TRACE_CAP = 8,          /* saln_wfa_affine_align_batch, saln_ends_free_align_batch: the pair's trace codes alone
                                     exceed trace_budget_bytes; score only, no CIGAR */
     SALN_INTERNAL = 9,           /* saln_wfa_affine_align_batch: the trace pass disagreed with
-                                    the score pass (internal inconsistency; never expected) */
+                                    the score pass; saln_ends_free_replay_align_batch: a walk
+                                    did not end within its rounds (internal inconsistency;
+                                    never expected) */
 
     SALN_E_INVALID = -1,   /* bad argument */
     SALN_E_HIP = -2,       /* HIP runtime error (message: saln_last_error) */
@@ -135,8 +137,8 @@ int saln_abi_version(void);
  * "nw.wide_min_pairs", "nw.rows_k", "nw.stripe_pk", "nw.spec",
  * "nw.spec_passes", "nw.spec_strict", "nw.avsa_narrow", "nw.rows_lone",
  * "nw.rows_xcd", "nw.avsa_profile", "nw.pk_tab", "nw.walk_waves",
- * "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb", "host.timing",
- * "host.prefault_mb".
+ * "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb", "ends_free.tile_rows",
+ * "host.timing", "host.prefault_mb".
  * Two levels, no other shared state:
  *  - saln_option_*: the process registry, the default of every context;
  *  - saln_context_option_*: overrides of one context (its own thread's
@@ -146,6 +148,9 @@ int saln_abi_version(void);
  * reach it.  SALN_E_INVALID for an unknown name or a value out of range.
  * The two ring-width options of the corrected WFA are stored within 0..4096,
  * but that engine runs only 0, 512, 1024 and 2048 (see saln_wfa_affine_batch).
+ * The tile-rows option of the ends-free replay traceback is stored within
+ * 64..1024, but that entry point runs only 64, 128, 256, 512 and 1024 (see
+ * saln_ends_free_replay_align_batch).
  * The arena option (MB, default 32768, minimum 1) bounds the tensor history
  * that one launch of the reference-semantics WFA (saln_wfa_*) keeps.  A lane
  * (one pair) of a pass with step cap s and width W holds S = s / 2 + 1 tensor
@@ -770,7 +775,7 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  * saln_ends_free_long_align_batch, below, whose only limit is the range
  * guard. */
 typedef struct {
-    int32_t score, status;            /* SALN_OK | SALN_TRACE_CAP */
+    int32_t score, status;            /* SALN_OK | SALN_TRACE_CAP | SALN_INTERNAL (replay only) */
     int32_t q_begin, q_end, db_begin, db_end;   /* begins -1 when no walk ran */
     uint32_t cigar_len, reserved;
 } saln_ends_free_result;              /* 32 bytes */
@@ -866,6 +871,43 @@ int saln_ends_free_long_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *b
  * range guard cannot hold for any scoring: len_q + len_db + 2 >= 2^30. */
 int saln_ends_free_long_pair_path(uint64_t len_q, uint64_t len_db, int32_t *long_fill,
                                   uint32_t *chunks);
+
+/* Alignments of long pairs without their n x m codes: the tiled replay
+ * traceback (ends_free_replay_kernels.hip, ends_free_replay_host.cpp).
+ * saln_ends_free_replay_align_batch is saln_ends_free_long_align_batch with
+ * another way to the words of a pair of the chunked fill: the same arguments,
+ * handle, records and words, word for word.  A pair within the class limits
+ * runs as under the other entry points.  A pair of the chunked fill is filled
+ * score only, keeping the boundary column of every chunk and, after every
+ * R-th db row, a checkpoint row (P and the next row's D of every column).
+ * The walk then runs tile by tile, a tile being one 1,024-column chunk times
+ * one block of R rows: a wave fills the tile's codes again from the checkpoint
+ * row above it and the boundary column left of it, the pair's walk follows
+ * them until it leaves the tile or ends, and the next round fills the tile it
+ * left for.  The host queues chunks + row blocks - 1 rounds of the chunk's
+ * largest pair, which is as many tiles as a walk can visit, and waits for
+ * none; a pair unfinished after them has status SALN_INTERNAL and no words
+ * (never expected).  R is option "ends_free.tile_rows": 64, 128, 256, 512 or
+ * 1024 (the default); with any other value the batch is SALN_E_INVALID.  Every
+ * allowed value gives the same results.
+ * trace_budget_bytes bounds a chunk's sum of saln_ends_free_replay_bytes; a
+ * pair whose footprint alone exceeds it gets score, ends, SALN_TRACE_CAP,
+ * begins -1 and no words.  want_cigar == 0: as the long entry point. */
+int saln_ends_free_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                      uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                      uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                      uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                                      uint64_t trace_budget_bytes, int want_cigar,
+                                      saln_ends_free_aln **out);
+/* Host only: the bytes one pair holds against trace_budget_bytes under the
+ * replay entry point, the one place they are computed (the batch's chunking
+ * asks it).  tile_rows: R, or 0 for the process registry's option value.  A pair
+ * within the class limits: saln_ends_free_trace_bytes.  Every other pair, with
+ * chunks = ceil(len_q / 1024): (chunks - 1) * len_db * 8 (boundary columns)
+ * + floor((len_db - 1) / R) * chunks * 1024 * 8 (checkpoint rows)
+ * + R * 512 (the tile in work); 0 when a sequence is empty.  SALN_E_INVALID as
+ * saln_ends_free_long_pair_path, and for an R outside the five values. */
+int saln_ends_free_replay_bytes(uint64_t len_q, uint64_t len_db, uint32_t tile_rows, uint64_t *bytes);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

@@ -144,6 +144,7 @@ EXPORTS = [
     "saln_ends_free_plan_destroy", "saln_ends_free_trace_bytes", "saln_ends_free_pair_geometry",
     "saln_ends_free_long_align_batch", "saln_ends_free_long_trace_bytes",
     "saln_ends_free_long_pair_path",
+    "saln_ends_free_replay_align_batch", "saln_ends_free_replay_bytes",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -309,6 +310,8 @@ def lib() -> C.CDLL:
         L.saln_ends_free_long_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
         L.saln_ends_free_long_pair_path.argtypes = [C.c_uint64, C.c_uint64,
                                                     C.POINTER(C.c_int32), u32p]
+        L.saln_ends_free_replay_align_batch.argtypes = L.saln_ends_free_align_batch.argtypes
+        L.saln_ends_free_replay_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u64p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

@@ -103,6 +103,43 @@ inline uint32_t ef_long_slots(uint64_t count, uint64_t ld_max) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({count, kEfLongWaves, fit}));
 }
 
+// Tiled replay traceback (ends_free_replay_kernels.hip, saln_ends_free_replay_*,
+// DESIGN.md section 3e): what a pair of the chunked path keeps in place of its
+// codes, from the pair's code_off on.  R: rows of a tile (a power of two).
+//   cols   the boundary columns 0 .. chunks - 2 (column c: P(r, c0), I(r, c0 + 1)
+//          of c0 = (c + 1) * 1024 for the rows 1 .. ld), ld int2 each
+//   cps    the checkpoint rows 0 .. (ld - 1) / R - 1 (row R * (n + 1): P(r, j),
+//          D(r + 1, j) of every column of every chunk), chunks * 1024 int2 each
+//   tile   the codes of the tile in work, R rows of kEfTileRowBytes
+// All three are multiples of 8 bytes.  A pair without a cell keeps nothing.
+constexpr uint32_t kEfTileRowBytes = (uint32_t)(kEfChunkCols / 2);
+struct EfReplayLayout {
+    uint64_t cols, cps, tile, bytes;  // byte offsets of the parts, and the whole
+};
+__host__ __device__ inline EfReplayLayout ef_replay_layout(uint64_t lq, uint64_t ld, uint64_t R) {
+    if (lq == 0 || ld == 0) return EfReplayLayout{0, 0, 0, 0};
+    const uint64_t chunks = (lq + kEfChunkCols - 1) / kEfChunkCols;
+    EfReplayLayout l;
+    l.cols = 0;
+    l.cps = (chunks - 1) * ld * 8;
+    l.tile = l.cps + (ld - 1) / R * chunks * kEfChunkCols * 8;
+    l.bytes = l.tile + R * kEfTileRowBytes;
+    return l;
+}
+inline bool ef_tile_rows_ok(int64_t R) {
+    return R == 64 || R == 128 || R == 256 || R == 512 || R == 1024;
+}
+
+// The resumable walk's state of one pair between two launches.
+struct EfWalkState {
+    uint32_t i, j;      // the cell the walk stands on, or whose code it waits for
+    uint32_t st, pend;  // state (0 M, 1 I, 2 D); the read still owed: kEfPend*
+    uint32_t run, op;   // the open run of words
+    uint32_t n, done;   // words written; 1: the record is final
+};
+static_assert(sizeof(EfWalkState) == 32, "EfWalkState layout");
+constexpr uint32_t kEfPendNone = 0, kEfPendArg = 1, kEfPendIExt = 2, kEfPendDExt = 3;
+
 // Dynamic LDS of a fill workgroup of `groups` lane groups: each group's db
 // row, padded by `lanes` bytes on both sides (the skew reads past the ends).
 inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
@@ -125,6 +162,30 @@ hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first
                                const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
                                uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s);
+// The forward pass of the tiled replay: the chunked fill, score only, of
+// pairs[first .. first + count), keeping each pair's boundary columns and
+// checkpoint rows at area + code_off (ef_replay_layout with tile_rows) and its
+// end state.  `slots` waves take pairs from *counter (zeroed on the stream).
+hipError_t launch_ef_fill_keep(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *area,
+                               uint32_t tile_rows, uint8_t *end_state, saln_ends_free_result *results,
+                               uint32_t slots, uint32_t *counter, hipStream_t s);
+// The replay's rounds over pairs[0 .. count), all of the chunked path, state
+// and lens indexed like pairs.  Start: the walk up to its first code read.
+// Tile: one wave per unfinished pair fills the tile of the cell it waits for.
+// Walk: every unfinished pair walks inside that tile, and finishes (record,
+// lens) or leaves it for a tile up or left.
+hipError_t launch_ef_replay_start(int32_t mode, const EfPair *pairs, uint32_t count,
+                                  const uint8_t *qs, const uint8_t *ds, const uint8_t *end_state,
+                                  saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
+                                  EfWalkState *state, hipStream_t s);
+hipError_t launch_ef_tile_fill(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
+                               const uint8_t *ds, EfScoring sc, uint8_t *area, uint32_t tile_rows,
+                               const EfWalkState *state, hipStream_t s);
+hipError_t launch_ef_tile_walk(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
+                               const uint8_t *ds, const uint8_t *area, uint32_t tile_rows,
+                               saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
+                               EfWalkState *state, hipStream_t s);
 // Walk of pairs[0 .. count): one pair per lane, from the end cell the fill
 // reported.  A pair's words end at words[cig_off + lq + ld), cigar_len of
 // them (also in lens, indexed like pairs).

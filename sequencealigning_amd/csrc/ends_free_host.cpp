@@ -114,10 +114,12 @@ uint64_t code_bytes(uint64_t lq, uint64_t ld) {
     return (ld * ef_row_bytes(lq) + 7) & ~7ull;
 }
 
-// The same under the long entry points, which own the long layout's size.
-uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok) {
+// The same under the long entry points, which own the long layout's size, and
+// (tile_rows != 0) under the replay entry point, which owns the footprint.
+uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok, uint32_t tile_rows) {
     uint64_t bytes = 0;
     if (!long_ok) return code_bytes(lq, ld);
+    if (tile_rows) return saln_ends_free_replay_bytes(lq, ld, tile_rows, &bytes) == SALN_OK ? bytes : 0;
     return saln_ends_free_long_trace_bytes(lq, ld, &bytes) == SALN_OK ? bytes : 0;
 }
 
@@ -249,12 +251,15 @@ int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
 
 // saln_ends_free_align_batch (long_ok = false) and
 // saln_ends_free_long_align_batch (true): the same batch, with or without the
-// chunked fill for the pairs the classes refuse.
+// chunked fill for the pairs the classes refuse.  saln_ends_free_replay_align_batch
+// (long_ok and tile_rows != 0): a chunk's bytes are the pairs' replay
+// footprints, and its pairs of the chunked path run ef_replay_run in place of
+// the fill with codes and ef_walk_kernel.
 int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                          const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                          const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
                          int32_t mode, const saln_nw_scoring *scoring, uint64_t trace_budget_bytes,
-                         int want_cigar, saln_ends_free_aln **out, bool long_ok) {
+                         int want_cigar, saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     EfScoring sc{};
@@ -282,10 +287,10 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     };
     std::vector<Chunk> chunks;
     Chunk plain;
-    std::vector<uint8_t> capped(n_pairs, 0);
+    std::vector<uint8_t> capped(n_pairs, 0), unfinished(tile_rows ? n_pairs : 0, 0);
     for (uint64_t k = 0; k < n_pairs; ++k) {
         EfPair p = all[k];
-        const uint64_t bytes = code_bytes(p.lq, p.ld, long_ok);
+        const uint64_t bytes = code_bytes(p.lq, p.ld, long_ok, tile_rows);
         if (!want_cigar || bytes > budget) {
             capped[k] = want_cigar ? 1 : 0;
             plain.pairs.push_back(p);
@@ -329,6 +334,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     auto *results = d_res.as<saln_ends_free_result>();
     std::vector<Launch> launches;
     EfLongWorkspace ws(ctx, s);
+    EfReplayWorkspace rws(ctx, s);
 
     if (!plain.pairs.empty()) {
         plan_launches(&plain.pairs, &launches, long_ok);
@@ -352,12 +358,25 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         // the fills and the walk read the same descriptors, in the fills' order
         plan_launches(&c.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, c.pairs.data(), n * sizeof(EfPair), hipMemcpyHostToDevice, s));
+        // replay: the pairs of the chunked path, the plan's last, walk tile by tile
+        uint32_t n_walk = n;
+        if (tile_rows)
+            while (!launches.empty() && launches.back().cls == kEfLongClass) {
+                n_walk = launches.back().first;
+                launches.pop_back();
+            }
         rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
                        d_state.as<uint8_t>(), results, s, &ws);
         if (rc != SALN_OK) return rc;
-        HIP_TRY(launch_ef_walk(mode, d_pairs.as<EfPair>(), n, sq, sd, d_codes.as<uint8_t>(),
+        HIP_TRY(launch_ef_walk(mode, d_pairs.as<EfPair>(), n_walk, sq, sd, d_codes.as<uint8_t>(),
                                d_state.as<uint8_t>(), results, d_words.as<uint32_t>(),
                                d_lens.as<uint32_t>(), s));
+        if (n_walk < n) {
+            rc = ef_replay_run(&rws, mode, c.pairs.data() + n_walk, d_pairs.as<EfPair>() + n_walk, n - n_walk,
+                               sq, sd, sc, d_codes.as<uint8_t>(), tile_rows, d_state.as<uint8_t>(), results,
+                               d_words.as<uint32_t>(), d_lens.as<uint32_t>() + n_walk, s);
+            if (rc != SALN_OK) return rc;
+        }
         lens.resize(n);
         HIP_TRY(hipMemcpyAsync(lens.data(), d_lens.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -370,6 +389,10 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         uint64_t total = 0;
         for (const uint32_t i : order) {
             const EfPair &p = c.pairs[i];
+            if (i >= n_walk && lens[i] == kEfWalkUnfinished) {  // never expected: no words
+                unfinished[p.out] = 1;
+                lens[i] = 0;
+            }
             lens[i] = std::min(lens[i], p.lq + p.ld);
             dst[i] = total;
             aln->off[p.out] = base + total;
@@ -394,6 +417,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     for (uint64_t k = 0; k < n_pairs; ++k) {
         saln_ends_free_result &r = aln->res[k];
         if (capped[k]) r.status = SALN_TRACE_CAP;
+        if (tile_rows && unfinished[k]) r.status = SALN_INTERNAL;
         if (aln->off[k] == kNoWords) {
             aln->off[k] = cur;
             r.cigar_len = 0;

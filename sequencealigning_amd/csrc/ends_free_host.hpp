@@ -1,6 +1,8 @@
-// What the two host files of the ends-free engine share: ends_free_host.cpp
-// (saln_ends_free_*, the batch itself) and ends_free_long_host.cpp
-// (saln_ends_free_long_*, the chunked fill's sizes, path and launches).
+// What the host files of the ends-free engine share: ends_free_host.cpp
+// (saln_ends_free_*, the batch itself), ends_free_long_host.cpp
+// (saln_ends_free_long_*, the chunked fill's sizes, path and launches) and
+// ends_free_replay_host.cpp (saln_ends_free_replay_*, the tiled replay's
+// footprint and rounds).
 #pragma once
 #include "ends_free.hpp"
 #include "host_common.hpp"
@@ -9,12 +11,15 @@ namespace saln {
 
 // The batch behind saln_ends_free_align_batch (long_ok = false: the classes'
 // limits and refusals) and saln_ends_free_long_align_batch (long_ok = true:
-// pairs above those limits run the chunked fill).  ends_free_host.cpp.
+// pairs above those limits run the chunked fill) and, with tile_rows != 0,
+// saln_ends_free_replay_align_batch (a chunk holds replay footprints, and the
+// alignments of its chunked-path pairs come from ef_replay_run).
+// ends_free_host.cpp.
 int ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                    const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                    const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
                    const saln_nw_scoring *scoring, uint64_t trace_budget_bytes, int want_cigar,
-                   saln_ends_free_aln **out, bool long_ok);
+                   saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows = 0);
 
 // Device workspace of a batch's chunked fills, all on one stream: the boundary
 // slots (grown to the largest launch's need) and the pair counter.
@@ -30,5 +35,27 @@ int ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint3
                  uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
                  const EfScoring &sc, uint8_t *d_codes, uint8_t *d_end_state,
                  saln_ends_free_result *d_results, hipStream_t s);
+
+// Device workspace of a batch's replays, all on one stream: the walks' states
+// and the forward pass's pair counter.
+struct EfReplayWorkspace {
+    DevBuf state, counter;
+    size_t state_bytes = 0;
+    EfReplayWorkspace(saln_context *ctx, hipStream_t s) : state(ctx, s), counter(ctx, s) {}
+};
+
+// What ef_replay_run leaves in lens for a pair whose walk did not end within
+// the rounds its lengths allow.
+constexpr uint32_t kEfWalkUnfinished = 0xFFFFFFFFu;
+
+// The tiled replay of `count` pairs of the chunked path (h_pairs on the host,
+// d_pairs the same on the device; code_off: each pair's replay area in
+// d_area): the forward pass, then the rounds of tile fill and tile walk, all
+// queued on s, none waited for.  Records, words and lens as the class walk
+// leaves them.  ends_free_replay_host.cpp.
+int ef_replay_run(EfReplayWorkspace *ws, int32_t mode, const EfPair *h_pairs, const EfPair *d_pairs,
+                  uint32_t count, const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc,
+                  uint8_t *d_area, uint32_t tile_rows, uint8_t *d_end_state,
+                  saln_ends_free_result *d_results, uint32_t *d_words, uint32_t *d_lens, hipStream_t s);
 
 }  // namespace saln

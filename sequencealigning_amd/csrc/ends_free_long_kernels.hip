@@ -51,7 +51,14 @@ static_assert(kLanes * kCols == (int)kEfChunkCols, "a chunk is one 64 x 16 fill"
 // runs at most 128 steps earlier) and written by lane 63 at step r + 62, both
 // by this wave in program order, so a row's old value is always consumed
 // before its new one is stored.
-template <int kMode, bool kCodes>
+//
+// kKeep (the forward pass of the tiled replay; score
+// only): bnd is the base of the pairs' replay areas and slot_rows the tile
+// rows R.  Lane 63 publishes into the pair's own column c (chunk c + 1 reads
+// it: no entry is overwritten), every lane stores Hp / Dn of its columns after
+// each row that is a multiple of R and below ld, and the end state is stored.
+// The instances without kKeep compile as before the flag (section 3e's table).
+template <int kMode, bool kCodes, bool kKeep = false>
 __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     __shared__ uint8_t ring[kRing];
     const int lane = (int)threadIdx.x;
-    int2 *col = bnd + (size_t)blockIdx.x * slot_rows;
+    int2 *col = kKeep ? bnd : bnd + (size_t)blockIdx.x * slot_rows;
     const int32_t o = sc.open, e = sc.extend;
     for (;;) {
         uint32_t gi = 0;
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         const uint8_t *__restrict__ q = qs + p.q_off;
         const uint8_t *__restrict__ d = ds + p.d_off;
         if (lq == 0) {  // no column: score 0 at the origin in every mode
-            if (lane == 0) ef_store_end<kCodes>(results, end_state, p.out, 0, 0u, 0u, 0u);
+            if (lane == 0) ef_store_end<kCodes || kKeep>(results, end_state, p.out, 0, 0u, 0u, 0u);
             continue;
         }
         const uint32_t nchunks = (lq + kEfChunkCols - 1) / (uint32_t)kEfChunkCols;
@@ -89,7 +96,20 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         int32_t rbest = 0;
         uint32_t rbest_j = 0;
         const int T = ld ? (int)ld + kLanes - 1 : 0;  // no row: the row-0 values stand
+        // kKeep: the pair's columns (colw written, col read) and checkpoint rows
+        int2 *colw = nullptr, *cps = nullptr;
+        uint32_t keep_mask = 0;
+        if constexpr (kKeep) {
+            const EfReplayLayout lay = ef_replay_layout(lq, ld, slot_rows);
+            colw = bnd + (p.code_off + lay.cols) / 8;
+            cps = bnd + (p.code_off + lay.cps) / 8;
+            keep_mask = (uint32_t)slot_rows - 1;
+        }
         for (uint32_t c = 0; c < nchunks; ++c) {
+            if constexpr (kKeep) {
+                col = colw;  // column c - 1, what the chunk before wrote
+                if (c > 0) colw += ld;
+            }
             const uint32_t col0 = c * (uint32_t)kEfChunkCols + (uint32_t)lane * K;  // my columns: col0+1 .. col0+K
             const bool publish = lane == kLanes - 1 && c + 1 < nchunks;
             uint32_t qc[K];
@@ -189,7 +209,17 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                         hd = inH;
                         pubF = F;
                         pubH = Hp[K - 1];
-                        if (publish) col[r - 1] = make_int2(pubH, pubF);
+                        if constexpr (kKeep) {
+                            if (publish) colw[r - 1] = make_int2(pubH, pubF);
+                            if (((uint32_t)r & keep_mask) == 0 && (uint32_t)r < ld) {
+                                int2 *cp = cps + ((size_t)((uint32_t)r / (uint32_t)slot_rows - 1) * nchunks + c) *
+                                                     kEfChunkCols + (size_t)lane * K;
+#pragma unroll
+                                for (int k = 0; k < K; ++k) cp[k] = make_int2(Hp[k], Dn[k]);
+                            }
+                        } else {
+                            if (publish) col[r - 1] = make_int2(pubH, pubF);
+                        }
                         if constexpr (kOverlap) {
                             const bool b = Msel > cbest;  // the smallest row wins a tie
                             cbest = b ? Msel : cbest;
@@ -236,10 +266,10 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         }
         const bool owner = (uint32_t)lane == l_end;  // of column lq, in the last chunk
         if constexpr (kOverlap) ef_overlap_end(owner, lq, ld, rbest, rbest_j, best, best_i, best_j);
-        ef_reduce_best<kLanes, kMode, kCodes>(lane, owner, best, best_i, best_j, best_st, lq, results, end_state,
+        ef_reduce_best<kLanes, kMode, kCodes || kKeep>(lane, owner, best, best_i, best_j, best_st, lq, results, end_state,
                                               p.out);
         // the next pair reuses the boundary column and the ring
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        if constexpr (!kKeep) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     }
 }
 
@@ -257,6 +287,21 @@ hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first
     return ef_with_mode(mode, [&](auto m) {
         constexpr int kMode = decltype(m)::value;
         return codes ? go(ef_fill_long_kernel<kMode, true>) : go(ef_fill_long_kernel<kMode, false>);
+    });
+}
+
+hipError_t launch_ef_fill_keep(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *area,
+                               uint32_t tile_rows, uint8_t *end_state, saln_ends_free_result *results,
+                               uint32_t slots, uint32_t *counter, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    if (slots == 0 || !area || !end_state || !counter || !ef_tile_rows_ok(tile_rows))
+        return hipErrorInvalidValue;
+    return ef_with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((ef_fill_long_kernel<decltype(m)::value, false, true>), dim3(slots), dim3(kLanes), 0,
+                           s, pairs, first, count, qs, ds, (uint8_t *)nullptr, end_state, results, sc,
+                           reinterpret_cast<int2 *>(area), (uint64_t)tile_rows, counter);
+        return hipGetLastError();
     });
 }
 

@@ -34,6 +34,7 @@ enum class Opt : int {
     Wfa2W1,             // "wfa2.w1": first-pass ring width (0 auto)
     Wfa2W2,             // "wfa2.w2": second-pass ring width (0 auto)
     WfaArenaMb,         // "wfa.arena_mb": MB of tensor history per launch (reference-semantics WFA)
+    EndsFreeTileRows,   // "ends_free.tile_rows": db rows of a tile of the replay traceback (64, 128, 256, 512, 1024)
     HostTiming,         // "host.timing": stage times of the host paths on stderr
     HostPrefaultMb,     // "host.prefault_mb": host buffer a new context faults in while HIP starts
     Count

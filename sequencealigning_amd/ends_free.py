@@ -28,7 +28,13 @@ tests/overlap_model.py.
 ``local_align_long``, ``semi_global_align_long`` and ``overlap_align_long`` take pairs of any length
 within the range guard ((n + m + 2) * max|parameter| < 2^30): a pair above the
 limits runs the chunked fill (ends_free_long_kernels.hip), every other pair
-the same fills as before, with the same records and words.
+the same fills as before, with the same records and words.  With
+``replay=True`` they call ``saln_ends_free_replay_align_batch``: a pair above
+the limits keeps boundary columns and checkpoint rows in place of its n x m
+trace codes and its alignment is walked tile by tile
+(ends_free_replay_kernels.hip; ``replay_bytes`` is what it holds against
+``trace_budget``, option ``ends_free.tile_rows`` the tile's db rows).  Records
+and words are the same.
 """
 from __future__ import annotations
 
@@ -109,19 +115,24 @@ def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace
 
 
 def ends_free_align_long_batch(queries, dbs, pairs=None, *, mode, scoring=None,
-                               trace_budget: int = 0, cigar: bool = True, device: int = 0):
+                               trace_budget: int = 0, cigar: bool = True, device: int = 0,
+                               replay: bool = False):
     """ends_free_align_batch without the length limits
     (saln_ends_free_long_align_batch): the same arguments and return.  A pair
     of at most 1,024 x 65,000 runs as there and gives the same record and
     words; every other pair runs the chunked fill.  The only limit is the
-    range guard."""
-    return _align_batch("saln_ends_free_long_align_batch", queries, dbs, pairs, mode, scoring,
-                        trace_budget, cigar, device)
+    range guard.  replay=True (saln_ends_free_replay_align_batch): the same
+    records and words, but a pair of the chunked fill holds replay_bytes, not
+    trace_bytes_long, against trace_budget, and its alignment comes from the
+    tiled replay; TRACE_CAP then means that replay_bytes alone exceed the
+    budget."""
+    entry = "saln_ends_free_replay_align_batch" if replay else "saln_ends_free_long_align_batch"
+    return _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar, device)
 
 
-def _one(seq1, seq2, mode, scoring, trace_budget, device, batch=ends_free_align_batch):
+def _one(seq1, seq2, mode, scoring, trace_budget, device, batch=ends_free_align_batch, **kw):
     res, cig = batch([seq1], [seq2], [(0, 0)], mode=mode, scoring=scoring,
-                     trace_budget=trace_budget, device=device)
+                     trace_budget=trace_budget, device=device, **kw)
     return res[0], cig[0]
 
 
@@ -145,20 +156,25 @@ def overlap_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: in
     return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device)
 
 
-def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
+                     replay: bool = False):
     """local_align for sequences of any length (ends_free_align_long_batch)."""
-    return _one(seq1, seq2, Mode.Local, scoring, trace_budget, device, ends_free_align_long_batch)
+    return _one(seq1, seq2, Mode.Local, scoring, trace_budget, device, ends_free_align_long_batch,
+                replay=replay)
 
 
-def semi_global_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+def semi_global_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
+                           replay: bool = False):
     """semi_global_align for sequences of any length (ends_free_align_long_batch)."""
     return _one(seq1, seq2, Mode.SemiGlobal, scoring, trace_budget, device,
-                ends_free_align_long_batch)
+                ends_free_align_long_batch, replay=replay)
 
 
-def overlap_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0):
+def overlap_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
+                       replay: bool = False):
     """overlap_align for sequences of any length (ends_free_align_long_batch)."""
-    return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device, ends_free_align_long_batch)
+    return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device, ends_free_align_long_batch,
+                replay=replay)
 
 
 def cigar_score(cigar, scoring=None) -> int:
@@ -191,6 +207,18 @@ def trace_bytes_long(len_q: int, len_db: int) -> int:
     out = C.c_uint64()
     _lib.check(_lib.lib().saln_ends_free_long_trace_bytes(int(len_q), int(len_db), C.byref(out)),
                "saln_ends_free_long_trace_bytes")
+    return out.value
+
+
+def replay_bytes(len_q: int, len_db: int, tile_rows: int = 0) -> int:
+    """saln_ends_free_replay_bytes: bytes one pair holds against trace_budget
+    under replay=True (host only).  trace_bytes within the class limits; above
+    them the boundary columns, the checkpoint rows and one tile of codes.
+    tile_rows 0: the value of option ends_free.tile_rows."""
+    out = C.c_uint64()
+    _lib.check(_lib.lib().saln_ends_free_replay_bytes(int(len_q), int(len_db), int(tile_rows),
+                                                      C.byref(out)),
+               "saln_ends_free_replay_bytes")
     return out.value
 
 

@@ -1,0 +1,281 @@
+"""CPU, no device: the host-only side of the ends-free replay traceback
+(saln_ends_free_replay_bytes, option ends_free.tile_rows) and the inputs of
+test_ends_free_replay_gpu.py with their preconditions, asserted from the plain
+models: which tile edge each constructed path crosses, and how.
+
+A tile is a 1,024-column chunk times a block of R db rows; the GPU file runs
+these inputs at R = 64, so "column 1,024" is a chunk edge and "row 64" a
+row-block edge."""
+import random
+
+import numpy as np
+import pytest
+
+import ends_free_model as model
+import overlap_model as omodel
+import test_ends_free_long as cpu
+
+LOCAL, SEMI, OVERLAP = model.LOCAL, model.SEMI_GLOBAL, omodel.OVERLAP
+MODES = [LOCAL, SEMI, OVERLAP]
+TILE_ROWS = (64, 128, 256, 512, 1024)
+CHUNK = 1024
+
+
+def _rand(rng, n, alphabet=b"ACGT"):
+    return bytes(rng.choice(alphabet) for _ in range(n))
+
+
+def align(q, d, mode, scheme=None):
+    """The plain model of the mode."""
+    return omodel.align(q, d, scheme) if mode == OVERLAP else model.align(q, d, mode, scheme)
+
+
+def components(n, m, R):
+    """The three stated parts of a chunked-path pair's footprint: boundary
+    columns, checkpoint rows, one tile of codes."""
+    chunks = (n + CHUNK - 1) // CHUNK
+    return (chunks - 1) * m * 8, (m - 1) // R * chunks * CHUNK * 8, R * (CHUNK // 2)
+
+
+def path_cells(a):
+    """The cells (i, j), 1-based, of an alignment's path, end cell first."""
+    i, j = a.db_begin, a.q_begin
+    cells = []
+    for n, op in a.cigar:
+        for _ in range(n):
+            i, j = i + (op in "=XD"), j + (op in "=XI")
+            cells.append((i, j, op))
+    assert (i, j) == (a.db_end, a.q_end)
+    return cells[::-1]
+
+
+def tiles(a, R=64):
+    """The tiles (chunk, row block) of the path's cells, in the walk's order
+    (row 0 has no codes and lies in no tile)."""
+    out = []
+    for i, j, _ in path_cells(a):
+        if i == 0:
+            continue
+        t = ((j - 1) // CHUNK, (i - 1) // R)
+        if not out or out[-1] != t:
+            out.append(t)
+    return out
+
+
+# ------------------------------------------------------------------ 1. replay_bytes
+def test_replay_bytes_empty_and_inside_the_class_limits(saln):
+    ef = saln.ends_free
+    for R in (0,) + TILE_ROWS:
+        assert ef.replay_bytes(0, 0, R) == ef.replay_bytes(0, 70000, R) == ef.replay_bytes(5000, 0, R) == 0
+        for n in (1, 160, 161, 256, 257, 512, 513, 1023, 1024):
+            for m in (1, 63, 300, 65000):
+                assert ef.replay_bytes(n, m, R) == ef.trace_bytes(n, m), (n, m, R)
+
+
+def test_replay_bytes_components_and_monotone(saln):
+    """Above the class limits the footprint is the sum of its parts (no less),
+    and it rises with either length.  Across the limits' edges it does NOT
+    rise for every shape, and cannot with the stated parts: inside the limits
+    a pair holds all its codes (1,024 x 65,000: 33,280,000 bytes), one column
+    or row further only columns, checkpoints and a tile (1,025 x 65,000 at
+    R = 1,024: 2,076,480 bytes).  It rises across the query edge where the
+    tile alone outweighs the codes, m * 512 <= R * 512; that is asserted."""
+    ef = saln.ends_free
+    for R in TILE_ROWS:
+        for n, m in [(1025, 1), (1025, 65), (2048, 64), (2049, 129), (3000, 200), (5, 65001),
+                     (1030, 65001), (5000, 100000), (20000, 20000)]:
+            b = ef.replay_bytes(n, m, R)
+            assert b >= sum(components(n, m, R)), (n, m, R)
+            assert b <= sum(components(n, m, R)) + 24 and b % 8 == 0, (n, m, R)
+            assert b <= ef.replay_bytes(n + 1, m, R) and b <= ef.replay_bytes(n, m + 1, R), (n, m, R)
+            assert b <= ef.replay_bytes(n + 1024, m, R) and b <= ef.replay_bytes(n, m + R, R), (n, m, R)
+        for n in (1026, 2047, 2048, 2049, 3072, 3073):          # along the chunk edges
+            assert ef.replay_bytes(n - 1, 200, R) <= ef.replay_bytes(n, 200, R) <= ef.replay_bytes(n + 1, 200, R)
+        for m in (R - 1, R, R + 1, 2 * R, 2 * R + 1):           # along the row-block edges
+            assert ef.replay_bytes(1025, m - 1, R) <= ef.replay_bytes(1025, m, R) <= ef.replay_bytes(1025, m + 1, R)
+        for m in (1, 2, 63, R):                                  # across the query limit
+            assert ef.replay_bytes(1024, m, R) <= ef.replay_bytes(1025, m, R) <= ef.replay_bytes(1026, m, R)
+    assert ef.replay_bytes(1024, 65000, 1024) == 33280000 and ef.replay_bytes(1025, 65000, 1024) == 2076480
+
+
+def test_replay_bytes_of_the_issue_shape(saln):
+    ef = saln.ends_free
+    n = m = 20000
+    assert sum(components(n, m, 1024)) == 6677248
+    assert ef.replay_bytes(n, m, 1024) * 20 <= ef.trace_bytes_long(n, m)
+    assert ef.trace_bytes_long(n, m) == 200000000
+
+
+def test_replay_bytes_default_is_the_option(saln, saln_opt):
+    from sequencealigning_amd import _lib
+    ef = saln.ends_free
+    R = _lib.get_option("ends_free.tile_rows")[0]
+    assert R in TILE_ROWS and _lib.get_option("ends_free.tile_rows")[1] == R
+    assert ef.replay_bytes(3000, 200) == ef.replay_bytes(3000, 200, R)
+    saln_opt("ends_free.tile_rows", 64)
+    assert ef.replay_bytes(3000, 200) == ef.replay_bytes(3000, 200, 64) != ef.replay_bytes(3000, 200, R)
+
+
+def test_replay_bytes_refusals(saln, saln_opt):
+    from sequencealigning_amd import _lib
+    ef = saln.ends_free
+
+    def refused(fn):
+        with pytest.raises(_lib.SalnError) as e:
+            fn()
+        assert e.value.code == _lib.E_INVALID and _lib.last_error() != ""
+        return _lib.last_error()
+
+    assert ef.pair_path_long((1 << 30) - 3 - 70000, 70000)[0] == 1
+    assert ef.replay_bytes((1 << 30) - 3 - 70000, 70000, 1024) > 0
+    for n, m in (((1 << 30) - 2 - 70000, 70000), (1 << 30, 0), (0, 1 << 40)):
+        refused(lambda: ef.pair_path_long(n, m))
+        refused(lambda: ef.replay_bytes(n, m, 64))
+    for R in (1, 32, 63, 65, 100, 192, 2048, 1 << 20):
+        assert "tile_rows" in refused(lambda: ef.replay_bytes(3000, 200, R))
+        assert "tile_rows" in refused(lambda: ef.replay_bytes(100, 100, R))
+    saln_opt("ends_free.tile_rows", 100)        # the registry stores it, the engine refuses it
+    assert "tile_rows" in refused(lambda: ef.replay_bytes(3000, 200))
+    assert ef.replay_bytes(3000, 200, 64) > 0
+    with pytest.raises(_lib.SalnError):
+        _lib.set_option("ends_free.tile_rows", 2048)
+
+
+# ------------------------------------------------ 2. the GPU file's inputs (R = 64)
+def corner_pair():
+    """db = q[960:1088]: the diagonal passes (64, 1024) -> (65, 1025), a chunk
+    edge and a row-block edge in one M step."""
+    rng = random.Random(0xC04E4)
+    q = _rand(rng, 1200)
+    return q, q[960:1088]
+
+
+def deletion_pair():
+    """A db window with ten extra bases at rows 60-69: a D run over row 64, in
+    columns just above 1,024."""
+    rng = random.Random(0xDE164)
+    q = _rand(rng, 1300)
+    return q, q[990:1049] + b"N" * 10 + q[1049:1149]
+
+
+def begin_on_edges_pair():
+    """Local: the alignment begins at q_begin = 1,024, db_begin = 64 (its
+    first cell is the first of tile (1, 1))."""
+    rng = random.Random(0xBE61)
+    w = _rand(rng, 100)
+    return b"N" * 1024 + w, b"R" * 64 + w
+
+
+def end_on_edges_pair(db_end):
+    """Local: db_end = 64 (the end cell in the last row of block 0) or 65 (in
+    the first row of block 1), q_end = 1,064."""
+    rng = random.Random(0xE2D)
+    w = _rand(rng, 64)
+    return b"N" * 1000 + w, b"R" * (db_end - 64) + w + b"R" * 10
+
+
+def row0_insertion_pair():
+    """Semi-global: the walk reaches row 0 at column 1,050; the rest of the
+    query is one insertion and needs no further tile."""
+    rng = random.Random(0x0E6)
+    w = _rand(rng, 100)
+    return b"N" * 1050 + w, w + _rand(rng, 100)
+
+
+def overlap_row0_pair():
+    """Overlap: a query suffix over a db prefix; the walk stops on row 0 at
+    column 1,200."""
+    rng = random.Random(0x0B0)
+    w = _rand(rng, 100)
+    return _rand(rng, 1200) + w, w + _rand(rng, 80)
+
+
+def overlap_col0_pair():
+    """Overlap: a db suffix over a query prefix; the walk stops on column 0 at
+    row 100."""
+    rng = random.Random(0x0C0)
+    w = _rand(rng, 80)
+    return w + _rand(rng, 1100), _rand(rng, 100) + w
+
+
+def budget_pairs():
+    """Six 3,000 x 200 pairs, each db a mutated window over a chunk edge."""
+    rng = random.Random(0xB0D6E7)
+    qs = [_rand(rng, 3000) for _ in range(6)]
+    ds = []
+    for k, q in enumerate(qs):
+        lo = (924, 1948)[k % 2]
+        w = bytearray(q[lo:lo + 200])
+        for x in range(7, 200, 23):
+            w[x] = ord("A") if w[x] != ord("A") else ord("C")
+        ds.append(bytes(w[:90] + w[93:] + b"GCA"))
+    assert all(len(d) == 200 for d in ds)
+    return qs, ds
+
+
+def test_corner_precondition():
+    q, d = corner_pair()
+    for mode in MODES:
+        a = align(q, d, mode)
+        if mode == SEMI:    # the whole query: the same diagonal between two insertions
+            assert a.cigar == [(960, "I"), (128, "="), (112, "I")] and (a.db_begin, a.db_end) == (0, 128)
+        else:
+            assert a.cigar == [(128, "=")] and (a.q_begin, a.q_end, a.db_begin, a.db_end) == (960, 1088, 0, 128)
+        cells = path_cells(a)
+        assert (65, 1025, "=") in cells and (64, 1024, "=") in cells
+        assert tiles(a)[-2:] == [(1, 1), (0, 0)]       # both edges in one step
+
+
+def test_gap_preconditions():
+    q, d = cpu.insertion_pair()
+    for mode in MODES:
+        a = align(q, d, mode)
+        assert a.cigar == [(1000, "="), (60, "I"), (400, "=")] and cpu.covers(a.cigar, "I", 1024)
+        assert (0, 16) in tiles(a) and (1, 16) in tiles(a)          # the I run crosses in row block 16
+    q, d = deletion_pair()
+    for mode in (LOCAL, OVERLAP):
+        a = align(q, d, mode)
+        assert a.cigar == [(59, "="), (10, "D"), (100, "=")] and (a.q_begin, a.db_begin) == (990, 0)
+    for mode in MODES:
+        a = align(q, d, mode)
+        dcells = [(i, j) for i, j, op in path_cells(a) if op == "D"]
+        assert {i for i, _ in dcells} >= set(range(60, 70)) and {j for _, j in dcells if j == 1049}
+        assert (1, 1) in tiles(a) and (1, 0) in tiles(a)             # the D run leaves the row block
+
+
+def test_begin_and_end_on_tile_edges_preconditions():
+    q, d = begin_on_edges_pair()
+    a = align(q, d, LOCAL)
+    assert (a.q_begin, a.db_begin, a.q_end, a.db_end) == (1024, 64, 1124, 164) and a.cigar == [(100, "=")]
+    assert tiles(a) == [(1, 2), (1, 1)]
+    for db_end in (64, 65):
+        q, d = end_on_edges_pair(db_end)
+        a = align(q, d, LOCAL)
+        assert (a.q_begin, a.q_end, a.db_begin, a.db_end) == (1000, 1064, db_end - 64, db_end)
+        assert tiles(a)[0] == (1, (db_end - 1) // 64) and tiles(a)[-1] == (0, 0)
+
+
+def test_border_preconditions():
+    q, d = row0_insertion_pair()
+    a = align(q, d, SEMI)
+    assert a.cigar == [(1050, "I"), (100, "=")] and a.db_begin == 0
+    q, d = overlap_row0_pair()
+    a = align(q, d, OVERLAP)
+    assert a.cigar == [(100, "=")] and (a.q_begin, a.db_begin, a.q_end, a.db_end) == (1200, 0, 1300, 100)
+    assert tiles(a) == [(1, 1), (1, 0)]
+    q, d = overlap_col0_pair()
+    a = align(q, d, OVERLAP)
+    assert a.cigar == [(80, "=")] and (a.q_begin, a.db_begin, a.q_end, a.db_end) == (0, 100, 80, 180)
+    assert tiles(a) == [(0, 2), (0, 1)]
+
+
+def test_budget_pairs_precondition(saln):
+    ef = saln.ends_free
+    qs, ds = budget_pairs()
+    assert ef.pair_path_long(3000, 200) == (1, 3)
+    assert sum(components(3000, 200, 64)) == 109696
+    assert ef.replay_bytes(3000, 200, 64) < 200000 < ef.trace_bytes_long(3000, 200) == 300800
+    for k, (q, d) in enumerate(zip(qs, ds)):
+        a = align(q, d, LOCAL)
+        edge = (1024, 2048)[k % 2]
+        assert a.q_begin < edge - 50 and edge + 50 < a.q_end and len(a.cigar) > 5
