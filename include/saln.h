@@ -909,6 +909,70 @@ int saln_ends_free_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, c
  * saln_ends_free_long_pair_path, and for an R outside the five values. */
 int saln_ends_free_replay_bytes(uint64_t len_q, uint64_t len_db, uint32_t tile_rows, uint64_t *bytes);
 
+/* Ends-free alignment under a substitution matrix (protein scoring under a
+ * BLOSUM or PAM style table, IUPAC nucleotide codes, transition /
+ * transversion scoring).  Everything above stays as it is written: the
+ * recurrences, the three modes, the tie rules, the walk's choices, the record,
+ * the limits, the chunking and the handle.  Only s(i, j) changes:
+ *   s(i, j) = score[code[d[i-1]]][code[q[j-1]]]
+ * row: the db symbol, column: the query symbol.  The matrix need not be
+ * symmetric.  '=' and 'X' in the words stay byte comparisons of d[i-1] and
+ * q[j-1], whatever the two bytes score (two different bytes of one symbol are
+ * 'X').  code is a total map of the 256 byte values into 0 .. n_sym - 1, so a
+ * kernel never indexes outside the table, also under the device-resident plan
+ * where the host does not see the sequences.
+ * Domain: 1 <= n_sym <= 32, reserved all 0, every code[] entry < n_sym,
+ * gap_open <= 0, gap_extend < 0 and at least one entry of
+ * score[0 .. n_sym)[0 .. n_sym) > 0; anything else is SALN_E_INVALID with a
+ * message.  Range guard: the engine's own, (n + m + 2) * max|parameter| < 2^30,
+ * the parameters being gap_open, gap_extend and the entries inside n_sym x
+ * n_sym.
+ * On the device the table has one more column, which the pad columns behind a
+ * query's end read; it is strictly negative in every row (the role mismatch < 0
+ * plays under the scalar scoring: a pad cell then never holds local's best). */
+typedef struct {
+    uint8_t n_sym;            /* 1 .. 32 */
+    uint8_t reserved[3];      /* 0 */
+    int32_t gap_open, gap_extend;
+    uint8_t code[256];        /* byte -> symbol, every entry < n_sym */
+    int8_t  score[32][32];    /* [db symbol][query symbol]; entries at or above n_sym ignored */
+} saln_sub_matrix;            /* 1,292 bytes */
+/* Host only (no device needed): the domain rules above.  *max_abs (optional):
+ * the largest magnitude among gap_open, gap_extend and the entries inside
+ * n_sym x n_sym, what the range guard multiplies.  Every entry point below
+ * calls it. */
+int saln_sub_matrix_check(const saln_sub_matrix *m, int32_t *max_abs);
+/* saln_ends_free_align_batch, saln_ends_free_long_align_batch and
+ * saln_ends_free_replay_align_batch under a matrix (NULL: SALN_E_INVALID; there
+ * is no default matrix).  Every other argument, the limits, the chunking,
+ * SALN_TRACE_CAP and the handle (saln_ends_free_aln_count / _get / _free) as
+ * there. */
+int saln_ends_free_sub_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                   uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                   uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                   uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                   uint64_t trace_budget_bytes, int want_cigar,
+                                   saln_ends_free_aln **out);
+int saln_ends_free_sub_long_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                        uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                        uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                        uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                        uint64_t trace_budget_bytes, int want_cigar,
+                                        saln_ends_free_aln **out);
+int saln_ends_free_sub_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                          uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                          uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                          uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                          uint64_t trace_budget_bytes, int want_cigar,
+                                          saln_ends_free_aln **out);
+/* saln_ends_free_plan_create under a matrix: the device-resident score-only
+ * form (the database-search shape).  The plan owns the table's device copy;
+ * saln_ends_free_execute and saln_ends_free_plan_destroy serve it unchanged. */
+int saln_ends_free_sub_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                   const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                   const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                                   const saln_sub_matrix *matrix, saln_ends_free_plan **out);
+
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`
  * (parse.rs:54-99): extension must be exactly fa|fasta|fna; '>' opens a record

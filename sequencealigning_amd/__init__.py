@@ -16,9 +16,9 @@ from .wfa import WfaAlignment, WfaPlan, wfa_align, wfa_align_batch
 from . import wfa_affine
 from .wfa_affine import wfa_affine_align, wfa_affine_align_batch
 from . import ends_free
-from .ends_free import (EndsFreePlan, ends_free_align_batch, ends_free_align_long_batch, local_align,
-                        local_align_long, overlap_align, overlap_align_long, semi_global_align,
-                        semi_global_align_long)
+from .ends_free import (EndsFreePlan, SubstitutionMatrix, alignment_score, ends_free_align_batch,
+                        ends_free_align_long_batch, local_align, local_align_long, overlap_align,
+                        overlap_align_long, semi_global_align, semi_global_align_long)
 from ._lib import get_option, option_names, options, set_option
 
 __all__ = [
@@ -27,7 +27,7 @@ __all__ = [
     "cigar_ops_string", "dense_mask", "n_w_align", "NwAllVsAll", "nw_score_all_vs_all", "nw_align_batch", "pack_csr", "render", "render_batch",
     "wfa", "WfaAlignment", "WfaPlan", "wfa_align", "wfa_align_batch", "wfa_affine",
     "wfa_affine_align", "wfa_affine_align_batch",
-    "ends_free", "EndsFreePlan", "ends_free_align_batch", "local_align", "semi_global_align",
+    "ends_free", "EndsFreePlan", "SubstitutionMatrix", "alignment_score", "ends_free_align_batch", "local_align", "semi_global_align",
     "ends_free_align_long_batch", "local_align_long", "semi_global_align_long",
     "overlap_align", "overlap_align_long",
     "get_option", "option_names", "options", "set_option",

@@ -111,6 +111,14 @@ class EndsFreeResult(C.Structure):
                 ("cigar_len", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SubMatrix(C.Structure):
+    """saln_sub_matrix: a substitution matrix of the ends-free engine;
+    score[db symbol][query symbol]."""
+    _fields_ = [("n_sym", C.c_uint8), ("reserved", C.c_uint8 * 3), ("gap_open", C.c_int32),
+                ("gap_extend", C.c_int32), ("code", C.c_uint8 * 256),
+                ("score", (C.c_int8 * 32) * 32)]
+
+
 ENDS_FREE_RESULT_DTYPE = [("score", "<i4"), ("status", "<i4"), ("q_begin", "<i4"), ("q_end", "<i4"),
                           ("db_begin", "<i4"), ("db_end", "<i4"), ("cigar_len", "<u4"),
                           ("reserved", "<u4")]
@@ -145,6 +153,8 @@ EXPORTS = [
     "saln_ends_free_long_align_batch", "saln_ends_free_long_trace_bytes",
     "saln_ends_free_long_pair_path",
     "saln_ends_free_replay_align_batch", "saln_ends_free_replay_bytes",
+    "saln_sub_matrix_check", "saln_ends_free_sub_align_batch", "saln_ends_free_sub_long_align_batch",
+    "saln_ends_free_sub_replay_align_batch", "saln_ends_free_sub_plan_create",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -312,6 +322,15 @@ def lib() -> C.CDLL:
                                                     C.POINTER(C.c_int32), u32p]
         L.saln_ends_free_replay_align_batch.argtypes = L.saln_ends_free_align_batch.argtypes
         L.saln_ends_free_replay_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u64p]
+        L.saln_sub_matrix_check.argtypes = [C.POINTER(SubMatrix), i32p]
+        sub_batch = list(L.saln_ends_free_align_batch.argtypes)
+        sub_batch[11] = C.POINTER(SubMatrix)
+        L.saln_ends_free_sub_align_batch.argtypes = sub_batch
+        L.saln_ends_free_sub_long_align_batch.argtypes = sub_batch
+        L.saln_ends_free_sub_replay_align_batch.argtypes = sub_batch
+        sub_plan = list(L.saln_ends_free_plan_create.argtypes)
+        sub_plan[9] = C.POINTER(SubMatrix)
+        L.saln_ends_free_sub_plan_create.argtypes = sub_plan
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

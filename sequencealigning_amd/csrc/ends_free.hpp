@@ -40,6 +40,36 @@ hipError_t ef_with_mode(int32_t mode, F &&f) {
     }
 }
 
+// A run-time flag as a compile-time constant, in ef_with_mode's style:
+// f(std::bool_constant<flag>{}).
+template <class F>
+hipError_t ef_with_flag(bool flag, F &&f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// Scoring under a substitution matrix (saln_sub_matrix, saln_ends_free_sub_*):
+// one device block per batch or plan, which the fills with kSub copy into LDS
+// once per workgroup.
+//   bytes 0 .. 255   code[]: byte -> symbol, every entry < n_sym <= 32
+//   then 32 rows (db symbol) of kEfSubStride bytes: score[db][query] in columns
+//   0 .. 31 and the pad column kEfSubPad.
+// Invariant: the pad column is strictly negative in every row (kEfSubPadScore).
+// Pad columns past the query take part in local's running best without a
+// mask; that is safe only because a pad cell's M = P(i-1, j-1) + s lies
+// strictly below a P of the pair, hence below some real M or at most 0, which
+// needs s < 0 whatever the matrix holds.  Entries outside n_sym x n_sym are
+// never indexed (code[] is total and checked on the host) and hold the pad
+// score too.
+// Stride: the lanes of a group stand on different rows, so their row bases
+// differ.  A 32-byte stride would put row r on bank 8 r mod 32, four distinct
+// bases for 32 rows; 36 bytes (9 dwords, odd) puts the 32 rows on 32 distinct
+// banks.
+constexpr uint32_t kEfSubSyms = 32, kEfSubPad = 32, kEfSubStride = 36;
+constexpr int8_t kEfSubPadScore = -1;
+constexpr uint32_t kEfSubCodeBytes = 256;
+constexpr uint32_t kEfSubBytes = kEfSubCodeBytes + kEfSubSyms * kEfSubStride;  // 1,408
+static_assert(kEfSubPad < kEfSubStride && kEfSubBytes % 16 == 0, "table layout");
+
 // Query classes: one pair per group of `lanes` lanes, `cols` query columns per
 // lane, the whole query in one chunk (the i32 lane classes of the NW table).
 struct EfClass {
@@ -146,6 +176,10 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
     return (uint64_t)groups * ((uint64_t)ld_max + 2u * (uint32_t)kEfClass[cls].lanes);
 }
 
+// Every fill below takes `sub` after the scoring: nullptr runs the
+// match / mismatch instances and reads sc whole; a device block of kEfSubBytes
+// (above) runs the kSub instances, which read sc.open and sc.extend only.
+
 // Fill of pairs[first .. first + count), all of class cls with dbs of at most
 // ld_max rows.  mode: SALN_MODE_LOCAL, _SEMI_GLOBAL or _OVERLAP (the host has
 // checked it).  codes == nullptr: score only.  end_state (with codes): the
@@ -153,23 +187,23 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
 // walk takes it from the end cell's own code instead.
 hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
-                          uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
+                          const uint8_t *sub, uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
                           hipStream_t s);
 // Chunked fill of pairs[first .. first + count) (any lengths): `slots` waves,
 // each with slot_rows (>= the longest db) 8-byte entries of bnd, taking pairs
 // from *counter, which the caller has zeroed on the stream.
 hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
-                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
-                               uint8_t *end_state, saln_ends_free_result *results, void *bnd,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, const uint8_t *sub,
+                               uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s);
 // The forward pass of the tiled replay: the chunked fill, score only, of
 // pairs[first .. first + count), keeping each pair's boundary columns and
 // checkpoint rows at area + code_off (ef_replay_layout with tile_rows) and its
 // end state.  `slots` waves take pairs from *counter (zeroed on the stream).
 hipError_t launch_ef_fill_keep(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
-                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *area,
-                               uint32_t tile_rows, uint8_t *end_state, saln_ends_free_result *results,
-                               uint32_t slots, uint32_t *counter, hipStream_t s);
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, const uint8_t *sub,
+                               uint8_t *area, uint32_t tile_rows, uint8_t *end_state,
+                               saln_ends_free_result *results, uint32_t slots, uint32_t *counter, hipStream_t s);
 // The replay's rounds over pairs[0 .. count), all of the chunked path, state
 // and lens indexed like pairs.  Start: the walk up to its first code read.
 // Tile: one wave per unfinished pair fills the tile of the cell it waits for.
@@ -180,8 +214,8 @@ hipError_t launch_ef_replay_start(int32_t mode, const EfPair *pairs, uint32_t co
                                   saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
                                   EfWalkState *state, hipStream_t s);
 hipError_t launch_ef_tile_fill(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
-                               const uint8_t *ds, EfScoring sc, uint8_t *area, uint32_t tile_rows,
-                               const EfWalkState *state, hipStream_t s);
+                               const uint8_t *ds, EfScoring sc, const uint8_t *sub, uint8_t *area,
+                               uint32_t tile_rows, const EfWalkState *state, hipStream_t s);
 hipError_t launch_ef_tile_walk(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
                                const uint8_t *ds, const uint8_t *area, uint32_t tile_rows,
                                saln_ends_free_result *results, uint32_t *words, uint32_t *lens,

@@ -36,16 +36,50 @@ __device__ __forceinline__ EfBest ef_best_row0(uint32_t lq, int32_t o, int32_t e
         return {0, 0u, 0u};
 }
 
-// Row 0 of the columns behind col0.  Returns hd = P(0, col0).
-template <int K, int kMode>
+// kSub (scoring under a substitution matrix, ends_free.hpp): the workgroup's
+// copy in LDS of the batch's block `sub`, code[] then the score rows; nullptr
+// and no LDS without kSub.  Every thread of the workgroup calls it, before any
+// of them leaves the kernel.
+template <bool kSub>
+__device__ __forceinline__ uint8_t *ef_sub_stage(const uint8_t *__restrict__ sub) {
+    if constexpr (kSub) {
+        __shared__ __attribute__((aligned(16))) uint8_t lds[kEfSubBytes];
+        for (uint32_t n = threadIdx.x; n < kEfSubBytes / 4; n += blockDim.x)
+            reinterpret_cast<uint32_t *>(lds)[n] = reinterpret_cast<const uint32_t *>(sub)[n];
+        __syncthreads();
+        return lds;
+    } else {
+        return nullptr;
+    }
+}
+
+// The staged form of a db byte under kSub: its symbol.
+__device__ __forceinline__ uint32_t ef_sub_code(const uint8_t *lds, uint32_t byte) {
+    return lds[byte & 0xFFu];
+}
+
+// s(i, j) under kSub: score[dch][qc], dch a staged db symbol and qc a column's
+// symbol or kEfSubPad.  `trow` is ef_sub_row(dch), once per row.  The mask
+// keeps the row inside the table also where the staged byte is a pad of the
+// staging that no row uses.
+__device__ __forceinline__ const int8_t *ef_sub_row(const uint8_t *lds, uint32_t dch) {
+    return reinterpret_cast<const int8_t *>(lds) + kEfSubCodeBytes + (dch & (kEfSubSyms - 1)) * kEfSubStride;
+}
+
+// Row 0 of the columns behind col0.  Returns hd = P(0, col0).  kSub: qc holds
+// the columns' symbols (sub: the block in LDS) and kEfSubPad in pad columns.
+template <int K, int kMode, bool kSub = false>
 __device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32_t lq, uint32_t col0,
                                            int32_t o, int32_t e, uint32_t (&qc)[K], int32_t (&Hp)[K],
-                                           int32_t (&Dn)[K]) {
+                                           int32_t (&Dn)[K], const uint8_t *sub = nullptr) {
     constexpr bool kSemi = kMode == SALN_MODE_SEMI_GLOBAL, kOverlap = kMode == SALN_MODE_OVERLAP;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const uint32_t j = col0 + k + 1;
-        qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
+        if constexpr (kSub)
+            qc[k] = j <= lq ? ef_sub_code(sub, q[j - 1]) : kEfSubPad;
+        else
+            qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
         // semi-global P(0, j) = I(0, j) = o + j e; local and overlap P = 0
         Hp[k] = !kSemi ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
         // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
@@ -84,14 +118,18 @@ __device__ __forceinline__ void ef_store_codes(uint8_t *to, const EfCodes<K> &c)
 // hd = P(r, col0) for row r + 1 and pubF = I(r, col0+K+1), pubH = P(r, col0+K)
 // for the right neighbour, updates the lane's best end cell, and with kCodes
 // leaves the cells' codes in `codes`.  k_end: the register of column lq in its
-// lane.
-template <int K, int kMode, bool kCodes>
+// lane.  kSub: dch is the row's db symbol, qc the columns' symbols, and s comes
+// from the block in LDS (sub) in place of sc.match / sc.mismatch.
+template <int K, int kMode, bool kCodes, bool kSub = false>
 __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, int32_t inF, int32_t inH,
                                        const EfScoring &sc, uint32_t k_end, uint32_t r,
                                        int32_t (&Hp)[K], int32_t (&Dn)[K], int32_t &hd, int32_t &pubF,
-                                       int32_t &pubH, EfBest &best, EfCodes<K> &codes) {
+                                       int32_t &pubH, EfBest &best, EfCodes<K> &codes,
+                                       const uint8_t *sub = nullptr) {
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     const int32_t o = sc.open, e = sc.extend;
+    const int8_t *trow = nullptr;
+    if constexpr (kSub) trow = ef_sub_row(sub, dch);
     int32_t F = inF;
     int32_t Msel = kEfNeg, Isel = kEfNeg;
     if constexpr (kCodes) {
@@ -100,7 +138,12 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int32_t M = ef_add(hd, qc[k] == dch ? sc.match : sc.mismatch);
+        int32_t s;
+        if constexpr (kSub)
+            s = trow[qc[k]];
+        else
+            s = qc[k] == dch ? sc.match : sc.mismatch;
+        const int32_t M = ef_add(hd, s);
         const int32_t I = F, D = Dn[k];
         const int32_t P3 = max(M, max(I, D));
         const int32_t P = kLocal ? max(P3, 0) : P3;

@@ -70,7 +70,32 @@ int check_mode(int32_t mode) {
     return SALN_E_INVALID;
 }
 
-int make_scoring(const saln_nw_scoring *s, EfScoring *out, uint64_t *max_abs) {
+// The device block of a matrix that saln_sub_matrix_check has passed
+// (ends_free.hpp: the layout and the pad column's invariant).
+std::vector<uint8_t> sub_block(const saln_sub_matrix &m) {
+    std::vector<uint8_t> b(kEfSubBytes, (uint8_t)kEfSubPadScore);
+    std::copy(m.code, m.code + 256, b.begin());
+    for (uint32_t r = 0; r < m.n_sym; ++r)
+        for (uint32_t c = 0; c < m.n_sym; ++c)
+            b[kEfSubCodeBytes + r * kEfSubStride + c] = (uint8_t)m.score[r][c];
+    return b;
+}
+
+// The scoring a batch or a plan runs under: sc (a matrix leaves match and
+// mismatch 0: its fills never read them), the range guard's factor, and the
+// matrix's device block (empty under the scalar scoring).
+int make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::vector<uint8_t> *block) {
+    block->clear();
+    if (src.is_sub) {
+        int32_t mx = 0;
+        const int rc = saln_sub_matrix_check(src.sub, &mx);
+        if (rc != SALN_OK) return rc;
+        *out = EfScoring{0, 0, src.sub->gap_open, src.sub->gap_extend};
+        *max_abs = (uint64_t)mx;
+        *block = sub_block(*src.sub);
+        return SALN_OK;
+    }
+    const saln_nw_scoring *s = src.scalar;
     const EfScoring sc = s ? EfScoring{s->match, s->mismatch, s->gap_open, s->gap_extend}
                            : EfScoring{5, -4, -8, -6};
     if (sc.match <= 0 || sc.mismatch >= 0 || sc.open > 0 || sc.extend >= 0) {
@@ -149,18 +174,18 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
 // The fills of `pairs` (device copy d_pairs, in plan_launches' order).  ws:
 // the chunked fill's workspace (launches of kEfLongClass need one).
 int run_fills(const std::vector<Launch> &launches, int32_t mode, const EfPair *d_pairs,
-              const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, uint8_t *d_codes,
-              uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
+              const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, const uint8_t *d_sub,
+              uint8_t *d_codes, uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
               EfLongWorkspace *ws = nullptr) {
     for (const Launch &l : launches) {
         if (l.cls == kEfLongClass) {
             if (!ws) return SALN_E_INVALID;
-            const int rc = ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+            const int rc = ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
                                         d_codes, d_end_state, d_results, s);
             if (rc != SALN_OK) return rc;
             continue;
         }
-        HIP_TRY(launch_ef_fill(l.cls, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc,
+        HIP_TRY(launch_ef_fill(l.cls, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
                                d_codes, d_end_state, d_results, s));
     }
     return SALN_OK;
@@ -174,7 +199,7 @@ struct saln_ends_free_plan {
     int32_t mode = SALN_MODE_LOCAL;
     uint64_t n = 0;
     std::vector<Launch> launches;
-    DevBuf d_pairs;
+    DevBuf d_pairs, d_sub;  // d_sub: the matrix's block (empty: scalar scoring)
 };
 
 // The result handle of saln_ends_free_align_batch: pair k's words are
@@ -204,18 +229,81 @@ int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes)
     return SALN_OK;
 }
 
+int saln_sub_matrix_check(const saln_sub_matrix *m, int32_t *max_abs) {
+    if (!m) {
+        set_error("ends_free: the substitution matrix is NULL");
+        return SALN_E_INVALID;
+    }
+    if (m->n_sym < 1 || m->n_sym > kEfSubSyms) {
+        set_error("ends_free: substitution matrix n_sym " + std::to_string(m->n_sym) +
+                  " is outside 1 .. " + std::to_string(kEfSubSyms));
+        return SALN_E_INVALID;
+    }
+    if (m->reserved[0] || m->reserved[1] || m->reserved[2]) {
+        set_error("ends_free: substitution matrix reserved bytes must be 0");
+        return SALN_E_INVALID;
+    }
+    for (int b = 0; b < 256; ++b)
+        if (m->code[b] >= m->n_sym) {
+            set_error("ends_free: substitution matrix code[" + std::to_string(b) + "] = " +
+                      std::to_string(m->code[b]) + " is not below n_sym " + std::to_string(m->n_sym));
+            return SALN_E_INVALID;
+        }
+    if (m->gap_open > 0 || m->gap_extend >= 0) {
+        set_error("ends_free: substitution matrix gaps {" + std::to_string(m->gap_open) + ", " +
+                  std::to_string(m->gap_extend) + "} are outside this engine's domain (gap_open <= 0, "
+                  "gap_extend < 0)");
+        return SALN_E_INVALID;
+    }
+    const auto mag = [](int64_t v) { return v < 0 ? -v : v; };
+    int64_t mx = std::max(mag(m->gap_open), mag(m->gap_extend));
+    bool positive = false;
+    for (uint32_t r = 0; r < m->n_sym; ++r)
+        for (uint32_t c = 0; c < m->n_sym; ++c) {
+            positive = positive || m->score[r][c] > 0;
+            mx = std::max(mx, mag(m->score[r][c]));
+        }
+    if (!positive) {
+        set_error("ends_free: substitution matrix has no entry > 0 inside n_sym x n_sym: no pair "
+                  "could score above 0");
+        return SALN_E_INVALID;
+    }
+    if (max_abs) *max_abs = (int32_t)std::min<int64_t>(mx, INT32_MAX);
+    return SALN_OK;
+}
+
 int saln_ends_free_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
                                const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
                                const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
                                const saln_nw_scoring *scoring, saln_ends_free_plan **out) {
+    return ef_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                          EfScoreSrc::of(scoring), out);
+}
+
+int saln_ends_free_sub_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                   const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                   const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                                   const saln_sub_matrix *matrix, saln_ends_free_plan **out) {
+    return ef_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                          EfScoreSrc::of(matrix), out);
+}
+
+}  // extern "C"
+
+int saln::ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off,
+                         uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                         uint64_t n_pairs, int32_t mode, const EfScoreSrc &scoring,
+                         saln_ends_free_plan **out) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     auto p = std::make_unique<saln_ends_free_plan>();
     p->ctx = ctx;
     p->d_pairs = DevBuf(ctx);
+    p->d_sub = DevBuf(ctx);
     uint64_t max_abs = 0;
+    std::vector<uint8_t> block;
     int rc = check_mode(mode);
-    if (rc == SALN_OK) rc = make_scoring(scoring, &p->sc, &max_abs);
+    if (rc == SALN_OK) rc = make_scoring(scoring, &p->sc, &max_abs, &block);
     std::vector<EfPair> pairs;
     if (rc == SALN_OK)
         rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &pairs);
@@ -228,9 +316,15 @@ int saln_ends_free_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_
         HIP_TRY(p->d_pairs.alloc(n_pairs * sizeof(EfPair)));
         HIP_TRY(hipMemcpy(p->d_pairs.p, pairs.data(), n_pairs * sizeof(EfPair), hipMemcpyHostToDevice));
     }
+    if (!block.empty()) {
+        HIP_TRY(p->d_sub.alloc(block.size()));
+        HIP_TRY(hipMemcpy(p->d_sub.p, block.data(), block.size(), hipMemcpyHostToDevice));
+    }
     *out = p.release();
     return SALN_OK;
 }
+
+extern "C" {
 
 int saln_ends_free_execute(saln_ends_free_plan *p, const uint8_t *d_q_seq, const uint8_t *d_db_seq,
                            saln_ends_free_result *d_results, void *stream) {
@@ -239,7 +333,7 @@ int saln_ends_free_execute(saln_ends_free_plan *p, const uint8_t *d_q_seq, const
     hipStream_t s = resolve_stream(stream, p->ctx);
     HIP_TRY(hipSetDevice(p->ctx->device));
     return run_fills(p->launches, p->mode, p->d_pairs.as<EfPair>(), d_q_seq, d_db_seq, p->sc,
-                     nullptr, nullptr, d_results, s);
+                     p->d_sub.as<uint8_t>(), nullptr, nullptr, d_results, s);
 }
 
 int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
@@ -258,14 +352,15 @@ int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
 int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                          const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                          const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
-                         int32_t mode, const saln_nw_scoring *scoring, uint64_t trace_budget_bytes,
+                         int32_t mode, const EfScoreSrc &scoring, uint64_t trace_budget_bytes,
                          int want_cigar, saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     EfScoring sc{};
     uint64_t max_abs = 0;
+    std::vector<uint8_t> block;
     int rc = check_mode(mode);
-    if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs);
+    if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs, &block);
     std::vector<EfPair> all;
     if (rc == SALN_OK)
         rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all, long_ok);
@@ -317,11 +412,16 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;  // every launch below runs on it: the blocks sync it alone
     DevBuf dq(ctx, s), dd(ctx, s), d_pairs(ctx, s), d_res(ctx, s), d_codes(ctx, s), d_words(ctx, s),
-        d_state(ctx, s), d_lens(ctx, s), d_dst(ctx, s), d_packed(ctx, s);
+        d_state(ctx, s), d_lens(ctx, s), d_dst(ctx, s), d_packed(ctx, s), d_sub(ctx, s);
     const auto min16 = [](size_t n) { return std::max<size_t>(n, 16); };
     HIP_TRY(upload_seqs(dq, dd, q_seq, q_off, n_q, db_seq, db_off, n_db, 16));
     HIP_TRY(d_pairs.alloc(min16(max_n * sizeof(EfPair))));
     HIP_TRY(d_res.alloc(min16(n_pairs * sizeof(saln_ends_free_result))));
+    if (!block.empty()) {  // the matrix, once per call; `block` outlives every sync below
+        HIP_TRY(d_sub.alloc(block.size()));
+        HIP_TRY(hipMemcpyAsync(d_sub.p, block.data(), block.size(), hipMemcpyHostToDevice, s));
+    }
+    const uint8_t *sub = d_sub.as<uint8_t>();
     if (!chunks.empty()) {
         HIP_TRY(d_codes.alloc(min16(max_bytes)));
         HIP_TRY(d_words.alloc(min16(max_words * sizeof(uint32_t))));
@@ -340,8 +440,8 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         plan_launches(&plain.pairs, &launches, long_ok);
         HIP_TRY(hipMemcpyAsync(d_pairs.p, plain.pairs.data(), plain.pairs.size() * sizeof(EfPair),
                                hipMemcpyHostToDevice, s));
-        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, nullptr, nullptr, results, s,
-                       &ws);
+        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, sub, nullptr, nullptr, results,
+                       s, &ws);
         if (rc != SALN_OK) return rc;
         HIP_TRY(hipStreamSynchronize(s));  // d_pairs and the host vector are reused
     }
@@ -365,7 +465,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
                 n_walk = launches.back().first;
                 launches.pop_back();
             }
-        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, d_codes.as<uint8_t>(),
+        rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, sub, d_codes.as<uint8_t>(),
                        d_state.as<uint8_t>(), results, s, &ws);
         if (rc != SALN_OK) return rc;
         HIP_TRY(launch_ef_walk(mode, d_pairs.as<EfPair>(), n_walk, sq, sd, d_codes.as<uint8_t>(),
@@ -373,7 +473,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
                                d_lens.as<uint32_t>(), s));
         if (n_walk < n) {
             rc = ef_replay_run(&rws, mode, c.pairs.data() + n_walk, d_pairs.as<EfPair>() + n_walk, n - n_walk,
-                               sq, sd, sc, d_codes.as<uint8_t>(), tile_rows, d_state.as<uint8_t>(), results,
+                               sq, sd, sc, sub, d_codes.as<uint8_t>(), tile_rows, d_state.as<uint8_t>(), results,
                                d_words.as<uint32_t>(), d_lens.as<uint32_t>() + n_walk, s);
             if (rc != SALN_OK) return rc;
         }
@@ -440,7 +540,17 @@ int saln_ends_free_align_batch(saln_context *ctx, const uint8_t *q_seq, const ui
                                uint64_t trace_budget_bytes, int want_cigar,
                                saln_ends_free_aln **out) {
     return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
-                          scoring, trace_budget_bytes, want_cigar, out, false);
+                          EfScoreSrc::of(scoring), trace_budget_bytes, want_cigar, out, false);
+}
+
+int saln_ends_free_sub_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                   uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                   uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                   uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                   uint64_t trace_budget_bytes, int want_cigar,
+                                   saln_ends_free_aln **out) {
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                          EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out, false);
 }
 
 uint64_t saln_ends_free_aln_count(const saln_ends_free_aln *a) { return a ? a->res.size() : 0; }

@@ -9,6 +9,17 @@
 
 namespace saln {
 
+// A batch's or a plan's scoring as the caller gave it: the scalar scheme
+// (sub == nullptr; scalar == nullptr selects the default {5, -4, -8, -6}) or a
+// substitution matrix (is_sub; sub == nullptr is the caller's error).
+struct EfScoreSrc {
+    const saln_nw_scoring *scalar = nullptr;
+    const saln_sub_matrix *sub = nullptr;
+    bool is_sub = false;
+    static EfScoreSrc of(const saln_nw_scoring *s) { return EfScoreSrc{s, nullptr, false}; }
+    static EfScoreSrc of(const saln_sub_matrix *m) { return EfScoreSrc{nullptr, m, true}; }
+};
+
 // The batch behind saln_ends_free_align_batch (long_ok = false: the classes'
 // limits and refusals) and saln_ends_free_long_align_batch (long_ok = true:
 // pairs above those limits run the chunked fill) and, with tile_rows != 0,
@@ -18,8 +29,14 @@ namespace saln {
 int ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                    const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                    const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
-                   const saln_nw_scoring *scoring, uint64_t trace_budget_bytes, int want_cigar,
+                   const EfScoreSrc &scoring, uint64_t trace_budget_bytes, int want_cigar,
                    saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows = 0);
+
+// The plan behind saln_ends_free_plan_create and saln_ends_free_sub_plan_create.
+// ends_free_host.cpp.
+int ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off,
+                   uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
+                   int32_t mode, const EfScoreSrc &scoring, saln_ends_free_plan **out);
 
 // Device workspace of a batch's chunked fills, all on one stream: the boundary
 // slots (grown to the largest launch's need) and the pair counter.
@@ -30,10 +47,11 @@ struct EfLongWorkspace {
 };
 
 // One chunked-fill launch of pairs[first .. first + count) with dbs of at most
-// ld_max rows: ef_long_slots waves.  ends_free_long_host.cpp.
+// ld_max rows: ef_long_slots waves.  d_sub here and below: the matrix's device
+// block, or nullptr under the scalar scoring.  ends_free_long_host.cpp.
 int ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint32_t first,
                  uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
-                 const EfScoring &sc, uint8_t *d_codes, uint8_t *d_end_state,
+                 const EfScoring &sc, const uint8_t *d_sub, uint8_t *d_codes, uint8_t *d_end_state,
                  saln_ends_free_result *d_results, hipStream_t s);
 
 // Device workspace of a batch's replays, all on one stream: the walks' states
@@ -55,7 +73,7 @@ constexpr uint32_t kEfWalkUnfinished = 0xFFFFFFFFu;
 // leaves them.  ends_free_replay_host.cpp.
 int ef_replay_run(EfReplayWorkspace *ws, int32_t mode, const EfPair *h_pairs, const EfPair *d_pairs,
                   uint32_t count, const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc,
-                  uint8_t *d_area, uint32_t tile_rows, uint8_t *d_end_state,
+                  const uint8_t *d_sub, uint8_t *d_area, uint32_t tile_rows, uint8_t *d_end_state,
                   saln_ends_free_result *d_results, uint32_t *d_words, uint32_t *d_lens, hipStream_t s);
 
 }  // namespace saln

@@ -26,13 +26,17 @@
 namespace saln {
 
 // kMode: SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
-template <int G, int K, int kMode, bool kCodes>
+// kSub: s(i, j) from the substitution-matrix block `sub` (ends_free.hpp), copied
+// into LDS once per workgroup; the staged db row and qc then hold symbols.  The
+// instances without kSub compile as before the flag.
+template <int G, int K, int kMode, bool kCodes, bool kSub = false>
 __global__ __launch_bounds__(256) void ef_fill_kernel(
     const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
-    uint32_t ld_max) {
+    uint32_t ld_max, const uint8_t *__restrict__ sub) {
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    uint8_t *ef_sub = ef_sub_stage<kSub>(sub);  // before any thread leaves
     const int gpb = (int)blockDim.x / G;
     const int lane = (int)threadIdx.x % G, grp = (int)threadIdx.x / G;
     const uint32_t gi = blockIdx.x * (uint32_t)gpb + (uint32_t)grp;
@@ -46,7 +50,12 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     }
     extern __shared__ uint8_t ef_drow[];  // [groups][G + ld_max + G] db bytes
     uint8_t *myrow = ef_drow + (size_t)grp * (ld_max + 2 * G) + G;
-    for (uint32_t i = (uint32_t)lane; i < ld; i += G) myrow[i] = d[i];
+    for (uint32_t i = (uint32_t)lane; i < ld; i += G) {
+        if constexpr (kSub)
+            myrow[i] = (uint8_t)ef_sub_code(ef_sub, d[i]);
+        else
+            myrow[i] = d[i];
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
@@ -57,7 +66,7 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     const uint32_t l_end = jend / K, k_end = jend % K;  // the lane and register of column lq
     uint32_t qc[K];
     int32_t Hp[K], Dn[K];
-    int32_t hd = ef_row0<K, kMode>(qs + p.q_off, lq, col0, o, e, qc, Hp, Dn);
+    int32_t hd = ef_row0<K, kMode, kSub>(qs + p.q_off, lq, col0, o, e, qc, Hp, Dn, ef_sub);
     // column 0, entering lane 0: P(i, 0) = 0 in every mode (the free start of
     // semi-global and overlap, local's floor); I(i, 1) opens from M(i, 0) = 0
     // in semi-global and overlap and is -inf in local
@@ -74,7 +83,8 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
         const int32_t inH = ef_shr1<G>(bH, pubH);  // P(r, col0)
         if (r >= 1 && r <= (int)ld) {
             EfCodes<K> row;
-            ef_row<K, kMode, kCodes>(qc, dch, inF, inH, sc, k_end, (uint32_t)r, Hp, Dn, hd, pubF, pubH, best, row);
+            ef_row<K, kMode, kCodes, kSub>(qc, dch, inF, inH, sc, k_end, (uint32_t)r, Hp, Dn, hd, pubF, pubH, best,
+                                           row, ef_sub);
             if constexpr (kCodes) {
                 // lanes wholly past the query store nothing
                 if (col0 < lq) ef_store_codes<K>(crow + (size_t)(r - 1) * p.row_bytes, row);
@@ -202,18 +212,23 @@ struct FillLaunch {
     saln_ends_free_result *results;
     EfScoring sc;
     uint32_t ld_max;
+    const uint8_t *sub;
 };
 
 template <int G, int K>
 hipError_t fill_class(const FillLaunch &a) {
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, a.grid, a.block, a.lds, a.s, a.pairs, a.first, a.count, a.qs, a.ds,
-                           a.codes, a.end_state, a.results, a.sc, a.ld_max);
+                           a.codes, a.end_state, a.results, a.sc, a.ld_max, a.sub);
         return hipGetLastError();
     };
     return ef_with_mode(a.mode, [&](auto m) {
-        constexpr int kMode = decltype(m)::value;
-        return a.codes ? go(ef_fill_kernel<G, K, kMode, true>) : go(ef_fill_kernel<G, K, kMode, false>);
+        return ef_with_flag(a.sub != nullptr, [&](auto sb) {
+            constexpr int kMode = decltype(m)::value;
+            constexpr bool kSub = decltype(sb)::value;
+            return a.codes ? go(ef_fill_kernel<G, K, kMode, true, kSub>)
+                           : go(ef_fill_kernel<G, K, kMode, false, kSub>);
+        });
     });
 }
 
@@ -221,17 +236,20 @@ hipError_t fill_class(const FillLaunch &a) {
 
 hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
-                          uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
+                          const uint8_t *sub, uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
                           hipStream_t s) {
     if (count == 0) return hipSuccess;
     if (cls < 0 || cls >= kEfClasses || ld_max > kEfMaxDb) return hipErrorInvalidValue;
     const uint32_t G = (uint32_t)kEfClass[cls].lanes;
     // as many groups per workgroup (of at most 256 lanes) as 64 KB of LDS stage rows for
+    // (the matrix block comes out of the same 64 KB; a single group's row of
+    // the longest dbs goes up to kEfSubBytes above them, far below a CU's LDS)
+    const uint64_t budget = (64u << 10) - (sub ? kEfSubBytes : 0u);
     uint32_t groups = 256u / G;
-    while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > (64u << 10)) --groups;
+    while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > budget) --groups;
     const size_t lds = (size_t)ef_lds_bytes(cls, groups, ld_max);
     const FillLaunch a{mode, dim3((count + groups - 1) / groups), dim3(groups * G), lds, s, pairs, first, count,
-                       qs, ds, codes, end_state, results, sc, ld_max};
+                       qs, ds, codes, end_state, results, sc, ld_max, sub};
     switch (cls) {
         case 0: return fill_class<16, 10>(a);
         case 1: return fill_class<16, 16>(a);

@@ -13,7 +13,7 @@ using namespace saln;
 
 int saln::ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint32_t first,
                        uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
-                       const EfScoring &sc, uint8_t *d_codes, uint8_t *d_end_state,
+                       const EfScoring &sc, const uint8_t *d_sub, uint8_t *d_codes, uint8_t *d_end_state,
                        saln_ends_free_result *d_results, hipStream_t s) {
     if (count == 0) return SALN_OK;
     const uint64_t slot_rows = ld_max ? ld_max : 1;
@@ -25,7 +25,7 @@ int saln::ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs,
     }
     if (!ws->counter.p) HIP_TRY(ws->counter.alloc(16));
     HIP_TRY(hipMemsetAsync(ws->counter.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(launch_ef_fill_long(mode, d_pairs, first, count, d_q, d_db, sc, d_codes, d_end_state,
+    HIP_TRY(launch_ef_fill_long(mode, d_pairs, first, count, d_q, d_db, sc, d_sub, d_codes, d_end_state,
                                 d_results, ws->bnd.p, slot_rows, slots, ws->counter.as<uint32_t>(), s));
     return SALN_OK;
 }
@@ -64,7 +64,17 @@ int saln_ends_free_long_align_batch(saln_context *ctx, const uint8_t *q_seq, con
                                     uint64_t trace_budget_bytes, int want_cigar,
                                     saln_ends_free_aln **out) {
     return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
-                          scoring, trace_budget_bytes, want_cigar, out, true);
+                          EfScoreSrc::of(scoring), trace_budget_bytes, want_cigar, out, true);
+}
+
+int saln_ends_free_sub_long_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                        uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                        uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                        uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                        uint64_t trace_budget_bytes, int want_cigar,
+                                        saln_ends_free_aln **out) {
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                          EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out, true);
 }
 
 }  // extern "C"

@@ -58,15 +58,21 @@ static_assert(kLanes * kCols == (int)kEfChunkCols, "a chunk is one 64 x 16 fill"
 // it: no entry is overwritten), every lane stores Hp / Dn of its columns after
 // each row that is a multiple of R and below ld, and the end state is stored.
 // The instances without kKeep compile as before the flag (section 3e's table).
-template <int kMode, bool kCodes, bool kKeep = false>
+//
+// kSub: s(i, j) from the substitution-matrix block `sub` (ends_free.hpp), copied
+// into LDS once per workgroup.  qc holds the columns' symbols and the ring the
+// db rows' symbols, translated as the refill stores them.  The instances
+// without kSub compile as before the flag (section 3f's table).
+template <int kMode, bool kCodes, bool kKeep = false, bool kSub = false>
 __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
-    int2 *bnd, uint64_t slot_rows, uint32_t *counter) {
+    int2 *bnd, uint64_t slot_rows, uint32_t *counter, const uint8_t *__restrict__ sub) {
     constexpr int K = kCols;
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     __shared__ uint8_t ring[kRing];
+    const uint8_t *ef_sub = ef_sub_stage<kSub>(sub);
     const int lane = (int)threadIdx.x;
     int2 *col = kKeep ? bnd : bnd + (size_t)blockIdx.x * slot_rows;
     const int32_t o = sc.open, e = sc.extend;
@@ -117,7 +123,10 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const uint32_t j = col0 + k + 1;
-                qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
+                if constexpr (kSub)
+                    qc[k] = j <= lq ? ef_sub_code(ef_sub, q[j - 1]) : kEfSubPad;
+                else
+                    qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
                 Hp[k] = kLocal || kOverlap ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
                 Dn[k] = kOverlap ? o + e : kEfNeg;  // overlap: D(1, j) opens from M(0, j) = 0
             }
@@ -128,7 +137,8 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
             // rise inside a chunk, so strict > keeps the smallest row, then
             // the smallest column.  (Local pad columns need no mask: a pad
             // cell's M lies strictly below some real M of the pair, so it can
-            // only displace a lane's value that is not the pair's best.)
+            // only displace a lane's value that is not the pair's best.  kSub:
+            // the table's pad column is negative in every row for this.)
             int32_t cbest = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
             uint32_t cbest_i = 0, cbest_k = kLocal ? 0u : 1u;  // semi-global: cbest_k is the end state
             uint8_t *crow = nullptr;
@@ -148,7 +158,10 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
             for (int t0 = 0; t0 < T; t0 += kLanes) {
                 // the refill.  One wave: its LDS accesses execute in program order
-                ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)dnext;
+                if constexpr (kSub)
+                    ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)ef_sub_code(ef_sub, dnext);
+                else
+                    ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)dnext;
                 bcur = bnext;
                 const uint32_t inext = min((uint32_t)t0 + kLanes + (uint32_t)lane, ld - 1);
                 dnext = d[inext];
@@ -173,9 +186,16 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                         int32_t F = inF;
                         int32_t Msel = kEfNeg, Isel = kEfNeg;
                         uint32_t nlo = 0, nhi = 0;
+                        const int8_t *trow = nullptr;
+                        if constexpr (kSub) trow = ef_sub_row(ef_sub, dch);
 #pragma unroll
                         for (int k = 0; k < K; ++k) {
-                            const int32_t M = ef_add(hd, qc[k] == dch ? sc.match : sc.mismatch);
+                            int32_t sij;
+                            if constexpr (kSub)
+                                sij = trow[qc[k]];
+                            else
+                                sij = qc[k] == dch ? sc.match : sc.mismatch;
+                            const int32_t M = ef_add(hd, sij);
                             const int32_t I = F, D = Dn[k];
                             const int32_t P3 = max(M, max(I, D));
                             const int32_t P = kLocal ? max(P3, 0) : P3;
@@ -274,34 +294,42 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
 }
 
 hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
-                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *codes,
-                               uint8_t *end_state, saln_ends_free_result *results, void *bnd,
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, const uint8_t *sub,
+                               uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s) {
     if (count == 0) return hipSuccess;
     if (slots == 0 || !bnd || !counter) return hipErrorInvalidValue;
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(slots), dim3(kLanes), 0, s, pairs, first, count, qs, ds, codes,
-                           end_state, results, sc, static_cast<int2 *>(bnd), slot_rows, counter);
+                           end_state, results, sc, static_cast<int2 *>(bnd), slot_rows, counter, sub);
         return hipGetLastError();
     };
     return ef_with_mode(mode, [&](auto m) {
-        constexpr int kMode = decltype(m)::value;
-        return codes ? go(ef_fill_long_kernel<kMode, true>) : go(ef_fill_long_kernel<kMode, false>);
+        return ef_with_flag(sub != nullptr, [&](auto sb) {
+            constexpr int kMode = decltype(m)::value;
+            constexpr bool kSub = decltype(sb)::value;
+            return codes ? go(ef_fill_long_kernel<kMode, true, false, kSub>)
+                         : go(ef_fill_long_kernel<kMode, false, false, kSub>);
+        });
     });
 }
 
 hipError_t launch_ef_fill_keep(int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
-                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, uint8_t *area,
-                               uint32_t tile_rows, uint8_t *end_state, saln_ends_free_result *results,
-                               uint32_t slots, uint32_t *counter, hipStream_t s) {
+                               const uint8_t *qs, const uint8_t *ds, EfScoring sc, const uint8_t *sub,
+                               uint8_t *area, uint32_t tile_rows, uint8_t *end_state,
+                               saln_ends_free_result *results, uint32_t slots, uint32_t *counter,
+                               hipStream_t s) {
     if (count == 0) return hipSuccess;
     if (slots == 0 || !area || !end_state || !counter || !ef_tile_rows_ok(tile_rows))
         return hipErrorInvalidValue;
     return ef_with_mode(mode, [&](auto m) {
-        hipLaunchKernelGGL((ef_fill_long_kernel<decltype(m)::value, false, true>), dim3(slots), dim3(kLanes), 0,
-                           s, pairs, first, count, qs, ds, (uint8_t *)nullptr, end_state, results, sc,
-                           reinterpret_cast<int2 *>(area), (uint64_t)tile_rows, counter);
-        return hipGetLastError();
+        return ef_with_flag(sub != nullptr, [&](auto sb) {
+            hipLaunchKernelGGL((ef_fill_long_kernel<decltype(m)::value, false, true, decltype(sb)::value>),
+                               dim3(slots), dim3(kLanes), 0, s, pairs, first, count, qs, ds, (uint8_t *)nullptr,
+                               end_state, results, sc, reinterpret_cast<int2 *>(area), (uint64_t)tile_rows,
+                               counter, sub);
+            return hipGetLastError();
+        });
     });
 }
 

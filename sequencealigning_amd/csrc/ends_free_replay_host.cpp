@@ -34,7 +34,8 @@ int check_tile_rows(int64_t R) {
 // (kEfWalkUnfinished in lens) is the caller's internal error, not waited for.
 int saln::ef_replay_run(EfReplayWorkspace *ws, int32_t mode, const EfPair *h_pairs,
                         const EfPair *d_pairs, uint32_t count, const uint8_t *d_q, const uint8_t *d_db,
-                        const EfScoring &sc, uint8_t *d_area, uint32_t tile_rows, uint8_t *d_end_state,
+                        const EfScoring &sc, const uint8_t *d_sub, uint8_t *d_area, uint32_t tile_rows,
+                        uint8_t *d_end_state,
                         saln_ends_free_result *d_results, uint32_t *d_words, uint32_t *d_lens,
                         hipStream_t s) {
     if (count == 0) return SALN_OK;
@@ -54,12 +55,12 @@ int saln::ef_replay_run(EfReplayWorkspace *ws, int32_t mode, const EfPair *h_pai
     auto *state = ws->state.as<EfWalkState>();
     HIP_TRY(hipMemsetAsync(ws->counter.p, 0, sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(d_lens, 0xFF, (size_t)count * sizeof(uint32_t), s));
-    HIP_TRY(launch_ef_fill_keep(mode, d_pairs, 0, count, d_q, d_db, sc, d_area, tile_rows, d_end_state,
+    HIP_TRY(launch_ef_fill_keep(mode, d_pairs, 0, count, d_q, d_db, sc, d_sub, d_area, tile_rows, d_end_state,
                                 d_results, std::min(count, kEfLongWaves), ws->counter.as<uint32_t>(), s));
     HIP_TRY(launch_ef_replay_start(mode, d_pairs, count, d_q, d_db, d_end_state, d_results, d_words, d_lens,
                                    state, s));
     for (uint64_t r = 0; r < rounds; ++r) {
-        HIP_TRY(launch_ef_tile_fill(mode, d_pairs, count, d_q, d_db, sc, d_area, tile_rows, state, s));
+        HIP_TRY(launch_ef_tile_fill(mode, d_pairs, count, d_q, d_db, sc, d_sub, d_area, tile_rows, state, s));
         HIP_TRY(launch_ef_tile_walk(mode, d_pairs, count, d_q, d_db, d_area, tile_rows, d_results, d_words,
                                     d_lens, state, s));
     }
@@ -82,18 +83,41 @@ int saln_ends_free_replay_bytes(uint64_t len_q, uint64_t len_db, uint32_t tile_r
     return SALN_OK;
 }
 
-int saln_ends_free_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
-                                      uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
-                                      uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
-                                      uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
-                                      uint64_t trace_budget_bytes, int want_cigar,
-                                      saln_ends_free_aln **out) {
+namespace {
+
+// The replay entry points: the batch with the context's tile rows.
+int replay_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
+                 const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                 const uint32_t *pair_db, uint64_t n_pairs, int32_t mode, const EfScoreSrc &scoring,
+                 uint64_t trace_budget_bytes, int want_cigar, saln_ends_free_aln **out) {
     if (!ctx) return SALN_E_INVALID;
     const int64_t R = ctx->opts.effective()[Opt::EndsFreeTileRows];
     const int rc = check_tile_rows(R);
     if (rc != SALN_OK) return rc;
     return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
                           scoring, trace_budget_bytes, want_cigar, out, true, (uint32_t)R);
+}
+
+}  // namespace
+
+int saln_ends_free_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                      uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                      uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                      uint64_t n_pairs, int32_t mode, const saln_nw_scoring *scoring,
+                                      uint64_t trace_budget_bytes, int want_cigar,
+                                      saln_ends_free_aln **out) {
+    return replay_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                        EfScoreSrc::of(scoring), trace_budget_bytes, want_cigar, out);
+}
+
+int saln_ends_free_sub_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                          uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                          uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                          uint64_t n_pairs, int32_t mode, const saln_sub_matrix *matrix,
+                                          uint64_t trace_budget_bytes, int want_cigar,
+                                          saln_ends_free_aln **out) {
+    return replay_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
+                        EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out);
 }
 
 }  // extern "C"

@@ -38,14 +38,16 @@ static_assert(kEfTileRowBytes == kLanes * kCols / 2, "a tile row holds a chunk's
 //                  columns; lane 0 takes the kept column's row r0, or 0 in column 0
 // The db and the column come through the chunked fill's refill: 64 rows ahead
 // in a register, the db's live rows in a 128-byte LDS ring.
-template <int kMode>
+// kSub: as the chunked fill's (the block `sub` in LDS, symbols in qc and the ring).
+template <int kMode, bool kSub = false>
 __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
     const EfPair *__restrict__ pairs, uint32_t count, const uint8_t *__restrict__ qs,
     const uint8_t *__restrict__ ds, EfScoring sc, uint8_t *__restrict__ area, uint32_t R,
-    const EfWalkState *__restrict__ state) {
+    const EfWalkState *__restrict__ state, const uint8_t *__restrict__ sub) {
     constexpr int K = kCols;
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL;
     __shared__ uint8_t ring[kRing];
+    const uint8_t *ef_sub = ef_sub_stage<kSub>(sub);
     const uint32_t gi = blockIdx.x;
     if (gi >= count) return;
     const EfWalkState ws = state[gi];
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
     const uint32_t col0 = c * (uint32_t)kEfChunkCols + (uint32_t)lane * K;  // my columns: col0+1 .. col0+K
     uint32_t qc[K];
     int32_t Hp[K], Dn[K];
-    int32_t hd = ef_row0<K, kMode>(q, lq, col0, o, e, qc, Hp, Dn);
+    int32_t hd = ef_row0<K, kMode, kSub>(q, lq, col0, o, e, qc, Hp, Dn, ef_sub);
     if (b > 0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -93,7 +95,10 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     for (int t0 = 0; t0 < T; t0 += kLanes) {
         // one wave: its LDS accesses execute in program order
-        ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)dnext;
+        if constexpr (kSub)
+            ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)ef_sub_code(ef_sub, dnext);
+        else
+            ring[((uint32_t)t0 + (uint32_t)lane) & (kRing - 1)] = (uint8_t)dnext;
         bcur = bnext;
         const uint32_t inext = min(r0 + (uint32_t)t0 + kLanes + (uint32_t)lane, ld - 1);
         dnext = d[inext];
@@ -113,8 +118,8 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
             const int32_t inH = ef_shr1<kLanes>(bH, pubH);  // P(r, col0)
             if (rr >= 1 && rr <= (int)nrows) {
                 EfCodes<K> row;
-                ef_row<K, kMode, true>(qc, dch, inF, inH, sc, 0u, r0 + (uint32_t)rr, Hp, Dn, hd, pubF, pubH,
-                                       unused, row);
+                ef_row<K, kMode, true, kSub>(qc, dch, inF, inH, sc, 0u, r0 + (uint32_t)rr, Hp, Dn, hd, pubF, pubH,
+                                             unused, row, ef_sub);
                 // lanes wholly past the query store nothing
                 if (col0 < lq) ef_store_codes<K>(crow + (size_t)(rr - 1) * kEfTileRowBytes, row);
             }
@@ -275,14 +280,16 @@ hipError_t launch_ef_replay_start(int32_t mode, const EfPair *pairs, uint32_t co
 }
 
 hipError_t launch_ef_tile_fill(int32_t mode, const EfPair *pairs, uint32_t count, const uint8_t *qs,
-                               const uint8_t *ds, EfScoring sc, uint8_t *area, uint32_t tile_rows,
-                               const EfWalkState *state, hipStream_t s) {
+                               const uint8_t *ds, EfScoring sc, const uint8_t *sub, uint8_t *area,
+                               uint32_t tile_rows, const EfWalkState *state, hipStream_t s) {
     if (count == 0) return hipSuccess;
     if (!area || !state || !ef_tile_rows_ok(tile_rows)) return hipErrorInvalidValue;
     return ef_with_mode(mode, [&](auto m) {
-        hipLaunchKernelGGL(ef_tile_fill_kernel<decltype(m)::value>, dim3(count), dim3(kLanes), 0, s, pairs,
-                           count, qs, ds, sc, area, tile_rows, state);
-        return hipGetLastError();
+        return ef_with_flag(sub != nullptr, [&](auto sb) {
+            hipLaunchKernelGGL((ef_tile_fill_kernel<decltype(m)::value, decltype(sb)::value>), dim3(count),
+                               dim3(kLanes), 0, s, pairs, count, qs, ds, sc, area, tile_rows, state, sub);
+            return hipGetLastError();
+        });
     });
 }
 

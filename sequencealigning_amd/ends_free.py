@@ -35,6 +35,13 @@ trace codes and its alignment is walked tile by tile
 (ends_free_replay_kernels.hip; ``replay_bytes`` is what it holds against
 ``trace_budget``, option ``ends_free.tile_rows`` the tile's db rows).  Records
 and words are the same.
+
+Every ``scoring=`` argument takes the 4-tuple above or a ``SubstitutionMatrix``
+(protein scoring under a BLOSUM or PAM style table, IUPAC codes, transition /
+transversion scoring): s(i, j) = scores[symbol of the db byte][symbol of the
+query byte], everything else as defined above; '=' and 'X' stay byte
+comparisons.  A matrix runs the ``saln_ends_free_sub_*`` entry points, a
+4-tuple exactly the ones it always ran.
 """
 from __future__ import annotations
 
@@ -50,6 +57,139 @@ DEFAULT_SCORING = (5, -4, -8, -6)
 TRACE_CAP = _lib.TRACE_CAP    # per-pair status: trace codes larger than the whole budget
 MAX_QUERY = 1024              # longest query (columns); saln_ends_free_pair_geometry
 OVERLAP = 4                   # SALN_MODE_OVERLAP: a mode value, not a records.Mode member
+
+
+class SubstitutionMatrix:
+    """A substitution matrix with its gap costs: scoring of the ends-free
+    functions in place of the (match, mismatch, gap_open, gap_extend) tuple.
+
+    alphabet: the symbols, one byte each, at most 31.  scores[a][b]: the db
+    symbol alphabet[a] against the query symbol alphabet[b], each within int8;
+    the table need not be symmetric.  A byte outside the alphabet maps to one
+    more symbol, which scores ``unknown`` against everything and everything
+    against it (default: the smallest entry).  case_insensitive: a letter of
+    the alphabet also stands for its other case.  Raises ValueError on a
+    duplicate symbol, an entry outside int8, a table that is not
+    len(alphabet) x len(alphabet), or more symbols than fit.
+
+    The engine's domain (gap_open <= 0, gap_extend < 0, some entry > 0) is
+    checked by the library when the matrix is used (SalnError, E_INVALID), and
+    by ``check()``."""
+
+    MAX_SYMBOLS = 31  # the 32nd is the unknown symbol
+
+    def __init__(self, alphabet: bytes, scores, gap_open: int, gap_extend: int, *, unknown=None,
+                 case_insensitive: bool = False):
+        alphabet = bytes(alphabet)
+        n = len(alphabet)
+        if n == 0:
+            raise ValueError("SubstitutionMatrix: the alphabet is empty")
+        if n > self.MAX_SYMBOLS:
+            raise ValueError(f"SubstitutionMatrix: {n} symbols, at most {self.MAX_SYMBOLS} fit "
+                             "(one more is the unknown symbol)")
+        rows = [list(r) for r in scores]
+        if len(rows) != n or any(len(r) != n for r in rows):
+            raise ValueError(f"SubstitutionMatrix: scores must be {n} x {n}, one row and one column "
+                             "per symbol of the alphabet")
+        table = [[int(v) for v in r] for r in rows]
+        if any(int(v) != v for r in rows for v in r):
+            raise ValueError("SubstitutionMatrix: entries must be integers")
+        flat = [v for r in table for v in r]
+        if unknown is None:
+            unknown = min(flat)
+        unknown = int(unknown)
+        for v in flat + [unknown]:
+            if not -128 <= v <= 127:
+                raise ValueError(f"SubstitutionMatrix: entry {v} is outside int8")
+        code = [n] * 256
+        seen = set()
+        for a, byte in enumerate(alphabet):
+            keys = {byte}
+            if case_insensitive:
+                keys |= {ord(chr(byte).lower()), ord(chr(byte).upper())} if byte < 128 else set()
+            if keys & seen:
+                raise ValueError(f"SubstitutionMatrix: duplicate symbol {bytes([byte])!r}")
+            seen |= keys
+            for k in keys:
+                code[k] = a
+        self.alphabet = alphabet
+        self.gap_open, self.gap_extend = int(gap_open), int(gap_extend)
+        self.unknown = unknown
+        self.case_insensitive = bool(case_insensitive)
+        self.n_sym = n + 1
+        self.code = code
+        # (n + 1) x (n + 1): the unknown symbol's row and column
+        self.table = [r + [unknown] for r in table] + [[unknown] * (n + 1)]
+
+    @classmethod
+    def from_ncbi(cls, text, gap_open: int, gap_extend: int, **kw):
+        """The usual text form of a matrix: '#' comment lines, a header line of
+        the symbols, then one row per symbol (the symbol, then its entries, in
+        the header's order): the row's symbol is the db symbol.  A '*' row or
+        column, if there is one, is not a symbol: its corner entry becomes
+        ``unknown`` unless that is given."""
+        if isinstance(text, bytes):
+            text = text.decode("ascii")
+        lines = [ln.split("#", 1)[0].split() for ln in text.splitlines()]
+        lines = [ln for ln in lines if ln]
+        if not lines:
+            raise ValueError("SubstitutionMatrix.from_ncbi: no header line")
+        header, body = lines[0], lines[1:]
+        if any(len(h) != 1 or ord(h) > 127 for h in header):
+            raise ValueError("SubstitutionMatrix.from_ncbi: the header must list one-byte symbols")
+        if len(body) != len(header):
+            raise ValueError(f"SubstitutionMatrix.from_ncbi: {len(header)} symbols in the header, "
+                             f"{len(body)} rows")
+        full = []
+        for h, row in zip(header, body):
+            if row[0] != h:
+                raise ValueError(f"SubstitutionMatrix.from_ncbi: row {row[0]!r} where the header "
+                                 f"has {h!r}")
+            if len(row) != len(header) + 1:
+                raise ValueError(f"SubstitutionMatrix.from_ncbi: row {h!r} has {len(row) - 1} "
+                                 f"entries, the header {len(header)} symbols")
+            try:
+                full.append([int(v) for v in row[1:]])
+            except ValueError:
+                raise ValueError(f"SubstitutionMatrix.from_ncbi: row {h!r} holds a non-integer") from None
+        keep = [k for k, h in enumerate(header) if h != "*"]
+        if len(keep) < len(header) and "unknown" not in kw:
+            star = header.index("*")
+            kw["unknown"] = full[star][star]
+        alphabet = "".join(header[k] for k in keep).encode("ascii")
+        return cls(alphabet, [[full[a][b] for b in keep] for a in keep], gap_open, gap_extend, **kw)
+
+    def s(self, db_byte: int, q_byte: int) -> int:
+        """The score of one db byte against one query byte."""
+        return self.table[self.code[db_byte]][self.code[q_byte]]
+
+    def c_struct(self) -> "_lib.SubMatrix":
+        """The saln_sub_matrix of this matrix."""
+        m = _lib.SubMatrix()
+        m.n_sym = self.n_sym
+        m.gap_open, m.gap_extend = self.gap_open, self.gap_extend
+        for b in range(256):
+            m.code[b] = self.code[b]
+        for a, row in enumerate(self.table):
+            for b, v in enumerate(row):
+                m.score[a][b] = v
+        return m
+
+    def check(self) -> int:
+        """saln_sub_matrix_check (host only): raises SalnError outside the
+        engine's domain; returns the range guard's largest |parameter|."""
+        mx = C.c_int32()
+        _lib.check(_lib.lib().saln_sub_matrix_check(C.byref(self.c_struct()), C.byref(mx)),
+                   "saln_sub_matrix_check")
+        return mx.value
+
+
+def _scoring_entry(entry: str, scoring):
+    """(entry point, scoring argument): the saln_ends_free_sub_* form of
+    `entry` under a SubstitutionMatrix, `entry` itself under a 4-tuple."""
+    if isinstance(scoring, SubstitutionMatrix):
+        return entry.replace("saln_ends_free_", "saln_ends_free_sub_", 1), C.pointer(scoring.c_struct())
+    return entry, _lib.scoring_arg(scoring)
 
 
 def _mode(mode) -> int:
@@ -73,9 +213,10 @@ def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar,
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
     L = _lib.lib()
     h = C.c_void_p()
+    entry, sarg = _scoring_entry(entry, scoring)
     _lib.check(getattr(L, entry)(
         _lib.context(device), vp(qs), vp(qo), len(qo) - 1, vp(ds), vp(do), len(do) - 1, vp(pq),
-        vp(pd), n, _mode(mode), _lib.scoring_arg(scoring), int(trace_budget), int(bool(cigar)),
+        vp(pd), n, _mode(mode), sarg, int(trace_budget), int(bool(cigar)),
         C.byref(h)), entry)
     try:
         res = np.zeros(n, dtype=_lib.ENDS_FREE_RESULT_DTYPE)
@@ -193,6 +334,52 @@ def cigar_score(cigar, scoring=None) -> int:
     return total
 
 
+def alignment_score(q, d, result_or_cigar, scoring=None, q_begin=None, db_begin=None) -> int:
+    """The score of an alignment recomputed from the sequences: q (query) and
+    d (db) as bytes, the alignment as its CIGAR ([(n, op)]) with q_begin and
+    db_begin, or as (result record, cigar) as the one-pair functions return it
+    (the begins then come from the record).  scoring: the 4-tuple or a
+    SubstitutionMatrix; under a matrix a column scores by its two bytes, which
+    cigar_score cannot know."""
+    if (isinstance(result_or_cigar, tuple) and len(result_or_cigar) == 2
+            and getattr(getattr(result_or_cigar[0], "dtype", None), "names", None)):
+        rec, cigar = result_or_cigar
+        q_begin = int(rec["q_begin"]) if q_begin is None else q_begin
+        db_begin = int(rec["db_begin"]) if db_begin is None else db_begin
+    else:
+        cigar = result_or_cigar
+    j, i = int(q_begin or 0), int(db_begin or 0)
+    q, d = bytes(q), bytes(d)
+    if isinstance(scoring, SubstitutionMatrix):
+        o, e, s = scoring.gap_open, scoring.gap_extend, scoring.s
+    else:
+        m, x, o, e = scoring if scoring is not None else DEFAULT_SCORING
+        s = lambda a, b: m if a == b else x  # noqa: E731
+    total, prev = 0, None
+    for n, op in cigar:
+        if op in "=X":
+            if j + n > len(q) or i + n > len(d):
+                raise ValueError("alignment_score: the alignment runs past a sequence's end")
+            for k in range(n):
+                if (q[j + k] == d[i + k]) != (op == "="):
+                    raise ValueError(f"alignment_score: '{op}' at query {j + k}, db {i + k} does not "
+                                     "agree with the bytes")
+                total += s(d[i + k], q[j + k])
+            i, j = i + n, j + n
+        elif op == "I":
+            total += e * n + (o if op != prev else 0)
+            j += n
+        elif op == "D":
+            total += e * n + (o if op != prev else 0)
+            i += n
+        else:
+            raise ValueError(f"alignment_score: unknown op {op!r}")
+        prev = op
+    if j > len(q) or i > len(d):
+        raise ValueError("alignment_score: the alignment runs past a sequence's end")
+    return total
+
+
 def trace_bytes(len_q: int, len_db: int) -> int:
     """saln_ends_free_trace_bytes: bytes of trace codes of one pair (host only)."""
     out = C.c_uint64()
@@ -247,7 +434,8 @@ class EndsFreePlan:
     """Device-resident score-only batch: plan from host offsets and a pair
     list once, execute on device (torch) sequence buffers into a device tensor
     of result records (n_pairs x 8 int32: score, status, q_begin = -1, q_end,
-    db_begin = -1, db_end, 0, 0)."""
+    db_begin = -1, db_end, 0, 0).  scoring: the 4-tuple or a SubstitutionMatrix
+    (saln_ends_free_sub_plan_create: the database-search shape)."""
 
     def __init__(self, q_off, db_off, pairs=None, *, mode, scoring=None, device: int = 0):
         L = _lib.lib()
@@ -259,10 +447,9 @@ class EndsFreePlan:
         self.n_pairs = n
         vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
         self._h = C.c_void_p()
-        _lib.check(L.saln_ends_free_plan_create(_lib.context(device), vp(qo), len(qo) - 1, vp(do),
-                                                len(do) - 1, vp(pq), vp(pd), n, _mode(mode),
-                                                _lib.scoring_arg(scoring), C.byref(self._h)),
-                   "saln_ends_free_plan_create")
+        entry, sarg = _scoring_entry("saln_ends_free_plan_create", scoring)
+        _lib.check(getattr(L, entry)(_lib.context(device), vp(qo), len(qo) - 1, vp(do), len(do) - 1,
+                                     vp(pq), vp(pd), n, _mode(mode), sarg, C.byref(self._h)), entry)
 
     def execute(self, d_q, d_db, d_results, stream=None):
         """d_q / d_db: device uint8 tensors (CSR bytes), d_results: device
