@@ -33,6 +33,11 @@ typedef enum {
     SALN_MODE_SEMI_GLOBAL = 2,
     SALN_MODE_OVERLAP = 4
 } saln_mode;
+/* Extension alignment of the ends-free engine (below): pinned at the origin,
+ * free at its end.  A macro beside the enum, not a member of it: saln_mode
+ * mirrors the reference's Mode plus overlap, and its list of members is
+ * pinned as it stands.  Every `int32_t mode` of saln_ends_free_* takes it. */
+#define SALN_MODE_EXTEND 8
 
 /* Per-pair status and API return codes.  The reference returns
  * AlignerError values (src/errors.rs:7-15) or panics (aborting the whole
@@ -758,6 +763,25 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  *    state is the first of M, I, D equal to P there.  At least one of
  *    q_begin and db_begin is 0, at least one of q_end = n and db_end = m
  *    holds.
+ *  - SALN_MODE_EXTEND (the gapped extension of seed-and-extend: pinned at the
+ *    origin, free at its end): the alignment starts at (0,0) and may stop at
+ *    any cell, with no charge for what lies behind the stop.  P = max(M, I,
+ *    D), no floor.  M(0,0) = 0 is the only start; I(0,j) = o + j e for j >= 1
+ *    (semi-global's row 0) and D(i,0) = o + i e for i >= 1 (column 0 is a
+ *    deletion run); M(i,0) for i > 0, M(0,j) for j > 0, I(i,0) and D(0,j) are
+ *    -infinity, hence I(i,1) = -infinity for i >= 1 and D(1,j) = -infinity
+ *    for j >= 1: nothing opens from a border gap.  score = max(0, max over
+ *    i >= 1, j >= 1 of M(i,j)); the smallest i, then the smallest j, wins a
+ *    tie (local's rule; ending in a gap is never better, e < 0).  No strictly
+ *    positive M (n = 0 or m = 0 included): the empty alignment, score 0, no
+ *    words, all four coordinates 0.  The walk starts in M at the end cell and
+ *    goes back to (0,0): in M at (i,j) it emits '=' or 'X' and goes to
+ *    (i-1,j-1); at (0,0) it stops, on row 0 with j > 0 it emits one run of j
+ *    'I' and stops, on column 0 with i > 0 one run of i 'D' and stops, else
+ *    the next state is the first of M, I, D equal to M(i,j) - s(i,j).
+ *    q_begin = db_begin = 0 always; the '=', 'X', 'I' lengths sum to q_end
+ *    and the '=', 'X', 'D' lengths to db_end.  X-drop / Z-drop termination is
+ *    not part of it: every cell is computed.
  * The walk's choice among co-optimal paths is fixed.  In M at (i,j): emit
  * '=' or 'X', v = M(i,j) - s(i,j), go to (i-1,j-1); local stops when v == 0,
  * semi-global on reaching column 0, overlap on reaching row 0 or column 0;
@@ -782,8 +806,9 @@ typedef struct {
 
 /* Pair conventions and argument errors as saln_wfa_affine_align_batch (NULL
  * pair lists = all-vs-all, db outer).  mode: SALN_MODE_LOCAL,
- * SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP; SALN_MODE_GLOBAL is
- * SALN_E_INVALID (use saln_nw_*), and so is every other value.
+ * SALN_MODE_SEMI_GLOBAL, SALN_MODE_OVERLAP or SALN_MODE_EXTEND;
+ * SALN_MODE_GLOBAL is SALN_E_INVALID (use saln_nw_*), and so is every other
+ * value.
  * want_cigar != 0: the fill stores 4-bit trace codes and the walk follows
  * them, in chunks: pairs are packed greedily in pair order into chunks of at
  * most trace_budget_bytes of codes (saln_ends_free_trace_bytes each; 0

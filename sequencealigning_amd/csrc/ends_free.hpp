@@ -28,7 +28,7 @@ struct EfScoring {
 };
 
 // The run-time mode as a compile-time constant: f(std::integral_constant<int,
-// SALN_MODE_...>{}) for the engine's three modes, hipErrorInvalidValue for
+// SALN_MODE_...>{}) for the engine's four modes, hipErrorInvalidValue for
 // anything else.  Every kernel template's instances are picked through it.
 template <class F>
 hipError_t ef_with_mode(int32_t mode, F &&f) {
@@ -36,6 +36,7 @@ hipError_t ef_with_mode(int32_t mode, F &&f) {
         case SALN_MODE_LOCAL: return f(std::integral_constant<int, SALN_MODE_LOCAL>{});
         case SALN_MODE_OVERLAP: return f(std::integral_constant<int, SALN_MODE_OVERLAP>{});
         case SALN_MODE_SEMI_GLOBAL: return f(std::integral_constant<int, SALN_MODE_SEMI_GLOBAL>{});
+        case SALN_MODE_EXTEND: return f(std::integral_constant<int, SALN_MODE_EXTEND>{});
         default: return hipErrorInvalidValue;
     }
 }
@@ -57,7 +58,9 @@ hipError_t ef_with_flag(bool flag, F &&f) {
 // Pad columns past the query take part in local's running best without a
 // mask; that is safe only because a pad cell's M = P(i-1, j-1) + s lies
 // strictly below a P of the pair, hence below some real M or at most 0, which
-// needs s < 0 whatever the matrix holds.  Entries outside n_sym x n_sym are
+// needs s < 0 whatever the matrix holds (extension's tracker, without the
+// floor, rests on the same column: ef_row in ends_free_fill.hpp has the
+// argument).  Entries outside n_sym x n_sym are
 // never indexed (code[] is total and checked on the host) and hold the pad
 // score too.
 // Stride: the lanes of a group stand on different rows, so their row bases
@@ -181,8 +184,8 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
 // (above) runs the kSub instances, which read sc.open and sc.extend only.
 
 // Fill of pairs[first .. first + count), all of class cls with dbs of at most
-// ld_max rows.  mode: SALN_MODE_LOCAL, _SEMI_GLOBAL or _OVERLAP (the host has
-// checked it).  codes == nullptr: score only.  end_state (with codes): the
+// ld_max rows.  mode: SALN_MODE_LOCAL, _SEMI_GLOBAL, _OVERLAP or _EXTEND (the
+// host has checked it).  codes == nullptr: score only.  end_state (with codes): the
 // state of each pair's end cell (0 M, 1 I), indexed like results; overlap's
 // walk takes it from the end cell's own code instead.
 hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,

@@ -10,7 +10,7 @@
 //
 // A lane holds K consecutive query columns col0+1 .. col0+K (col0 absolute) in
 // registers: qc their bases, Hp = P(r-1, j), Dn = D(r, j).  kMode is
-// SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
+// SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL, SALN_MODE_OVERLAP or SALN_MODE_EXTEND.
 #pragma once
 #include "ends_free_dev.hpp"
 
@@ -23,6 +23,7 @@ namespace saln {
 //                first; k is the end state (0 M, 1 I)
 //   overlap      P(i, lq) in that lane, strictly positive (the last row's
 //                candidates: ef_last_row_best)
+//   extend       local's: every M(i, j), strictly positive, no floor below it
 struct EfBest {
     int32_t v;
     uint32_t i, k;
@@ -72,7 +73,9 @@ template <int K, int kMode, bool kSub = false>
 __device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32_t lq, uint32_t col0,
                                            int32_t o, int32_t e, uint32_t (&qc)[K], int32_t (&Hp)[K],
                                            int32_t (&Dn)[K], const uint8_t *sub = nullptr) {
-    constexpr bool kSemi = kMode == SALN_MODE_SEMI_GLOBAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    // extension's row 0 is semi-global's: P(0, j) = I(0, j), D(1, j) = -inf
+    constexpr bool kSemi = kMode == SALN_MODE_SEMI_GLOBAL || kMode == SALN_MODE_EXTEND;
+    constexpr bool kOverlap = kMode == SALN_MODE_OVERLAP;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const uint32_t j = col0 + k + 1;
@@ -80,7 +83,7 @@ __device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32
             qc[k] = j <= lq ? ef_sub_code(sub, q[j - 1]) : kEfSubPad;
         else
             qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
-        // semi-global P(0, j) = I(0, j) = o + j e; local and overlap P = 0
+        // semi-global and extend P(0, j) = I(0, j) = o + j e; local and overlap P = 0
         Hp[k] = !kSemi ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
         // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
         Dn[k] = kOverlap ? o + e : kEfNeg;
@@ -120,6 +123,22 @@ __device__ __forceinline__ void ef_store_codes(uint8_t *to, const EfCodes<K> &c)
 // leaves the cells' codes in `codes`.  k_end: the register of column lq in its
 // lane.  kSub: dch is the row's db symbol, qc the columns' symbols, and s comes
 // from the block in LDS (sub) in place of sc.match / sc.mismatch.
+//
+// Extend keeps local's tracker (every M, strict > from 0) without local's
+// floor, and its pad columns still need no mask.  Claim: a pad cell's M lies
+// strictly below a real M(i, j), i, j >= 1, of the pair, or below 0, so it
+// never is the pair's best and never ties with it; it can only displace a
+// lane's value that is not the pair's best.  Every real P(i, j) is a real M,
+// or an I or D value, which is some M of its row or column plus o + L e < 0,
+// hence strictly below it, or it comes from a border, and the borders are
+// P(0, 0) = 0 and o + j e < 0, o + i e < 0.  So a real P is at most a real M
+// or at most 0, also where P(i-1, lq) is an I or D value.  The first pad
+// column's M = P(i-1, lq) + s with s < 0 (mismatch < 0; under kSub the table's
+// pad column) lies strictly below that; the pad cells' I and D lie strictly
+// below an M of a real or a pad cell, and further pad columns follow by
+// induction.  Nothing of this wraps: every pad value is at least
+// kEfNeg - (m + 3) max|parameter| (D(i, j) >= D(1, j) + (i - 1) e bounds P
+// from below in every column), which the range guard keeps above -2^31.
 template <int K, int kMode, bool kCodes, bool kSub = false>
 __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, int32_t inF, int32_t inH,
                                        const EfScoring &sc, uint32_t k_end, uint32_t r,
@@ -127,6 +146,7 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
                                        int32_t &pubH, EfBest &best, EfCodes<K> &codes,
                                        const uint8_t *sub = nullptr) {
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    constexpr bool kEveryM = kLocal || kMode == SALN_MODE_EXTEND;  // the tracker over every M
     const int32_t o = sc.open, e = sc.extend;
     const int8_t *trow = nullptr;
     if constexpr (kSub) trow = ef_sub_row(sub, dch);
@@ -155,7 +175,7 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
             c |= D >= tO ? kEfDExt : 0u;
             codes.w[k / 8] |= c << (4 * (k % 8));
         }
-        if constexpr (kLocal) {
+        if constexpr (kEveryM) {
             // rows and columns come in increasing order: > keeps the
             // smallest row, then the smallest column, of my columns
             const bool b = M > best.v;
@@ -180,7 +200,7 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
         const bool b = Msel > best.v;  // the smallest row wins a tie
         best.v = b ? Msel : best.v;
         best.i = b ? r : best.i;
-    } else if constexpr (!kLocal) {
+    } else if constexpr (!kEveryM) {
         const int32_t v = max(Msel, Isel);
         const bool b = v > best.v;  // the smallest row wins a tie
         best.v = b ? v : best.v;
@@ -240,7 +260,7 @@ __device__ __forceinline__ void ef_store_end(saln_ends_free_result *__restrict__
 }
 
 // The group's end cell from its lanes' (v, row i, absolute column j), and the
-// record.  Local and overlap: the largest value, then the smallest row, then
+// record.  Local, overlap and extend: the largest value, then the smallest row, then
 // the smallest column (lanes met a row at different steps: the row index
 // decides, not the step); lanes without a positive cell lose to every real
 // cell, and a pair without one ends at the origin with score 0.  Semi-global:

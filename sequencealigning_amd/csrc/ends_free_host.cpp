@@ -1,9 +1,9 @@
 // C ABI of the ends-free engine (include/saln.h, saln_ends_free_*): local,
-// semi-global and overlap affine-gap alignment.  Not a reference-parity path -
-// the reference only declares the first two modes
-// (needleman_wunsch_affine.rs:238-239, :331-332, :433-434) and has no overlap;
-// the checkers are the plain models tests/ends_free_model.py and
-// tests/overlap_model.py.
+// semi-global, overlap and extension affine-gap alignment.  Not a
+// reference-parity path - the reference only declares the first two modes
+// (needleman_wunsch_affine.rs:238-239, :331-332, :433-434) and has no overlap
+// and no extension; the checkers are the plain models tests/ends_free_model.py,
+// tests/overlap_model.py and tests/extend_model.py.
 //
 // A batch's pairs are grouped by query class (ef_class_of) and, within a
 // class, ordered by falling db length and cut where the length's power-of-two
@@ -60,7 +60,8 @@ void plan_launches(std::vector<EfPair> *pairs, std::vector<Launch> *out, bool lo
 }
 
 int check_mode(int32_t mode) {
-    if (mode == SALN_MODE_LOCAL || mode == SALN_MODE_SEMI_GLOBAL || mode == SALN_MODE_OVERLAP)
+    if (mode == SALN_MODE_LOCAL || mode == SALN_MODE_SEMI_GLOBAL || mode == SALN_MODE_OVERLAP ||
+        mode == SALN_MODE_EXTEND)
         return SALN_OK;
     if (mode == SALN_MODE_GLOBAL)
         set_error("ends_free: SALN_MODE_GLOBAL is not an ends-free mode; global alignment is "

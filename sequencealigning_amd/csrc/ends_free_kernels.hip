@@ -1,8 +1,9 @@
 // Kernels of the ends-free engine (include/saln.h, saln_ends_free_*): Gotoh
 // affine-gap alignment with free ends, local (Smith-Waterman), semi-global
-// (the whole query against a free db substring) and overlap (dovetail: all
-// four ends free, no floor).  NOT a reference-parity path: the reference only
-// declares the first two modes.  DESIGN.md section 3 holds the recurrences,
+// (the whole query against a free db substring), overlap (dovetail: all
+// four ends free, no floor) and extend (pinned at the origin, free at its
+// end: the gapped extension of seed-and-extend).  NOT a reference-parity
+// path: the reference only declares the first two modes.  DESIGN.md section 3 holds the recurrences,
 // the tie rules and the code layout.
 //
 // Fill: the decomposition of the NW i32 lane fill.  One pair per group of G
@@ -13,8 +14,9 @@
 // columns; the group reduces them at the end on (value, row, column), never
 // on the step.  Row 0, a lane's row, the code store and the end cell are those
 // of ends_free_fill.hpp (the chunked fill shares the end cell and keeps a row
-// of its own); this kernel adds the group's db row staged in LDS, constants on
-// lane 0's boundary (column 0) and the one pass over the rows.
+// of its own); this kernel adds the group's db row staged in LDS, lane 0's
+// boundary (column 0: constants, but extend's deletion run o + r e) and the one
+// pass over the rows.
 //
 // Walk: one pair per lane, from the reported end cell along the 4-bit codes.
 #include <hip/hip_runtime.h>
@@ -25,7 +27,8 @@
 
 namespace saln {
 
-// kMode: SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL or SALN_MODE_OVERLAP.
+// kMode: SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL, SALN_MODE_OVERLAP or
+// SALN_MODE_EXTEND.
 // kSub: s(i, j) from the substitution-matrix block `sub` (ends_free.hpp), copied
 // into LDS once per workgroup; the staged db row and qc then hold symbols.  The
 // instances without kSub compile as before the flag.
@@ -36,6 +39,7 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
     uint32_t ld_max, const uint8_t *__restrict__ sub) {
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    constexpr bool kExtend = kMode == SALN_MODE_EXTEND;
     uint8_t *ef_sub = ef_sub_stage<kSub>(sub);  // before any thread leaves
     const int gpb = (int)blockDim.x / G;
     const int lane = (int)threadIdx.x % G, grp = (int)threadIdx.x / G;
@@ -67,10 +71,12 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     uint32_t qc[K];
     int32_t Hp[K], Dn[K];
     int32_t hd = ef_row0<K, kMode, kSub>(qs + p.q_off, lq, col0, o, e, qc, Hp, Dn, ef_sub);
-    // column 0, entering lane 0: P(i, 0) = 0 in every mode (the free start of
-    // semi-global and overlap, local's floor); I(i, 1) opens from M(i, 0) = 0
-    // in semi-global and overlap and is -inf in local
-    const int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
+    // column 0, entering lane 0: P(i, 0) = 0 (the free start of semi-global
+    // and overlap, local's floor); I(i, 1) opens from M(i, 0) = 0 in
+    // semi-global and overlap and is -inf in local.  Extend: column 0 is a
+    // deletion run, P(r, 0) = D(r, 0) = o + r e with r = t + 1 the row of lane 0
+    // at step t (bHx below), and I(r, 1) is -inf: M(r, 0) is
+    const int32_t bH = 0, bF = kLocal || kExtend ? kEfNeg : o + e;
     int32_t pubF = kEfNeg, pubH = kEfNeg;
     EfBest best = ef_best_row0<kMode>(lq, o, e);
     uint8_t *crow = nullptr;
@@ -80,7 +86,8 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
         const int r = t - lane + 1;
         const uint32_t dch = myrow[t - lane];  // d[r-1]; the pads cover rows outside the db
         const int32_t inF = ef_shr1<G>(bF, pubF);  // I(r, col0+1)
-        const int32_t inH = ef_shr1<G>(bH, pubH);  // P(r, col0)
+        const int32_t bHx = kExtend ? o + (t + 1) * e : bH;
+        const int32_t inH = ef_shr1<G>(bHx, pubH);  // P(r, col0)
         if (r >= 1 && r <= (int)ld) {
             EfCodes<K> row;
             ef_row<K, kMode, kCodes, kSub>(qc, dch, inF, inH, sc, k_end, (uint32_t)r, Hp, Dn, hd, pubF, pubH, best,
@@ -121,6 +128,7 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
     // the fill's end cell, kept inside the matrix whatever the record holds
     uint32_t i = min((uint32_t)max(res.db_end, 0), p.ld), j = min((uint32_t)max(res.q_end, 0), p.lq);
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    constexpr bool kExtend = kMode == SALN_MODE_EXTEND;
     uint32_t st = end_state[p.out] & 1u;  // 0 M, 1 I, 2 D
     uint32_t n = 0, run = 0, op = 0;
     auto emit = [&](uint32_t o, uint32_t len) {
@@ -133,7 +141,7 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
         op = o;
         run = len;
     };
-    if ((kLocal || kOverlap) && res.score <= 0) i = j = 0;
+    if ((kLocal || kOverlap || kExtend) && res.score <= 0) i = j = 0;
     if constexpr (kOverlap) {
         // the end state is the end cell's own code: the first of M, I, D equal to P
         if (i > 0 && j > 0) st = ef_code(codes, p, i, j) & kEfArgMask;
@@ -141,8 +149,8 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
     while (j > 0) {
         if (i == 0) {
             // row 0.  Overlap: a free start, in M or after a D run that opened
-            // there.  Semi-global: the rest of the query is one insertion.
-            // (Local never stands here: its D(1, j) is -inf.)
+            // there.  Semi-global and extend: the rest of the query is one
+            // insertion.  (Local never stands here: its D(1, j) is -inf.)
             if constexpr (!kOverlap) {
                 if (!kLocal) emit(SALN_CIGAR_I, j);
                 j = 0;
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
                 // local: P = 0 on the border, the alignment begins here;
                 // overlap: every cell of row 0 and column 0 is a free start
                 if (kLocal || kOverlap) break;
-                st = 1;  // semi-global row 0 is I; column 0 ends the loop
+                st = 1;  // semi-global and extend: row 0 is I; column 0 ends the loop
                 continue;
             }
             const uint32_t a = ef_code(codes, p, i, j) & kEfArgMask;
@@ -174,6 +182,12 @@ __global__ __launch_bounds__(64) void ef_walk_kernel(
             // -inf and a D run never reaches row 0
             st = i > 0 && (ef_code(codes, p, i, j) & kEfDExt) ? 2u : 0u;
         }
+    }
+    if constexpr (kExtend) {
+        // column 0 above the origin is one deletion run, D(i, 0) = o + i e.  Only
+        // a diagonal step arrives here: I(i, 1) is -inf below row 0
+        emit(SALN_CIGAR_D, i);
+        i = 0;
     }
     if (run && n < cap) w[cap - ++n] = (run << 4) | op;
     res.q_begin = (int32_t)j;

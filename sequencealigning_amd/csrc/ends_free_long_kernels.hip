@@ -16,9 +16,9 @@
 //  - the db is not staged whole: a 128-byte LDS ring holds the rows that are
 //    live in the skew (t - 63 .. t at step t), refilled every 64 steps from a
 //    register loaded 64 steps ahead;
-//  - local's best cell: a best per chunk on strict > (rows rise inside a
-//    chunk), merged into the running best on (value, row) at the chunk's end,
-//    before the reduction over the lanes;
+//  - local's and extend's best cell: a best per chunk on strict > (rows rise
+//    inside a chunk), merged into the running best on (value, row) at the
+//    chunk's end, before the reduction over the lanes;
 //  - overlap's end cell: the owner of column n (in the last chunk) keeps the
 //    best P(r, n) as semi-global's does; every lane takes the last row's
 //    candidates from Hp after each chunk's last row, merged on strict > so
@@ -71,6 +71,8 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
     int2 *bnd, uint64_t slot_rows, uint32_t *counter, const uint8_t *__restrict__ sub) {
     constexpr int K = kCols;
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    constexpr bool kExtend = kMode == SALN_MODE_EXTEND;
+    constexpr bool kEveryM = kLocal || kExtend;  // the tracker over every M (ef_row)
     __shared__ uint8_t ring[kRing];
     const uint8_t *ef_sub = ef_sub_stage<kSub>(sub);
     const int lane = (int)threadIdx.x;
@@ -93,12 +95,12 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
         const uint32_t jend = lq - 1;
         // the lane and register of column lq in the last chunk
         const uint32_t l_end = jend % (uint32_t)kEfChunkCols / K, k_end = jend % K;
-        // running best.  local: best_j is the absolute column.  semi-global:
-        // the single owner restarts from row 0 in every chunk, the last counts.
+        // running best.  local and extend: best_j is the absolute column.
+        // semi-global: the single owner restarts from row 0 in every chunk, the last counts.
         // overlap: the owner of column lq as semi-global's (strictly positive
         // cells only), and rbest / rbest_j, the best of the last row so far
-        int32_t best = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
-        uint32_t best_i = 0, best_j = 0, best_st = kLocal ? 0u : 1u;  // row 0 ends in I
+        int32_t best = kEveryM || kOverlap ? 0 : o + (int32_t)lq * e;
+        uint32_t best_i = 0, best_j = 0, best_st = kEveryM ? 0u : 1u;  // row 0 ends in I
         int32_t rbest = 0;
         uint32_t rbest_j = 0;
         const int T = ld ? (int)ld + kLanes - 1 : 0;  // no row: the row-0 values stand
@@ -127,6 +129,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                     qc[k] = j <= lq ? ef_sub_code(ef_sub, q[j - 1]) : kEfSubPad;
                 else
                     qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
+                // extend's row 0 is semi-global's
                 Hp[k] = kLocal || kOverlap ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
                 Dn[k] = kOverlap ? o + e : kEfNeg;  // overlap: D(1, j) opens from M(0, j) = 0
             }
@@ -138,9 +141,10 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
             // the smallest column.  (Local pad columns need no mask: a pad
             // cell's M lies strictly below some real M of the pair, so it can
             // only displace a lane's value that is not the pair's best.  kSub:
-            // the table's pad column is negative in every row for this.)
-            int32_t cbest = kLocal || kOverlap ? 0 : o + (int32_t)lq * e;
-            uint32_t cbest_i = 0, cbest_k = kLocal ? 0u : 1u;  // semi-global: cbest_k is the end state
+            // the table's pad column is negative in every row for this.
+            // Extend's, without the floor, neither: the argument at ef_row.)
+            int32_t cbest = kEveryM || kOverlap ? 0 : o + (int32_t)lq * e;
+            uint32_t cbest_i = 0, cbest_k = kEveryM ? 0u : 1u;  // semi-global: cbest_k is the end state
             uint8_t *crow = nullptr;
             if constexpr (kCodes) crow = codes + p.code_off + (size_t)c * (kEfChunkCols / 2) + (size_t)lane * (K / 2);
             // rows t + 64 .. t + 127 of the db and of the boundary column,
@@ -172,10 +176,12 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                     const int s = t - t0;
                     const int r = t - lane + 1;
                     const uint32_t dch = ring[(uint32_t)(t - lane) & (kRing - 1)];  // d[r-1]
-                    // column c0 entering lane 0.  Chunk 0: P(i, 0) = 0 in every
-                    // mode, I(i, 1) opens from M(i, 0) = 0 in semi-global and overlap
-                    // and is -inf in local.  Later chunks: what lane 63 published for row t + 1
-                    int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;
+                    // column c0 entering lane 0.  Chunk 0: P(i, 0) = 0 but in
+                    // extend, I(i, 1) opens from M(i, 0) = 0 in semi-global and overlap
+                    // and is -inf in local.  Extend: the deletion run P(r, 0) = o + r e
+                    // of lane 0's row r = t + 1, and I(r, 1) = -inf.  Later chunks: what
+                    // lane 63 published for row t + 1
+                    int32_t bH = kExtend ? o + (t + 1) * e : 0, bF = kEveryM ? kEfNeg : o + e;
                     if (c > 0) {
                         bH = __builtin_amdgcn_readlane(bcur.x, s);
                         bF = __builtin_amdgcn_readlane(bcur.y, s);
@@ -210,7 +216,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                                 else
                                     nhi |= cd << (4 * (k - 8));
                             }
-                            if constexpr (kLocal) {
+                            if constexpr (kEveryM) {
                                 const bool b = M > cbest;
                                 cbest = b ? M : cbest;
                                 cbest_i = b ? (uint32_t)r : cbest_i;
@@ -244,7 +250,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                             const bool b = Msel > cbest;  // the smallest row wins a tie
                             cbest = b ? Msel : cbest;
                             cbest_i = b ? (uint32_t)r : cbest_i;
-                        } else if constexpr (!kLocal) {
+                        } else if constexpr (!kEveryM) {
                             const int32_t v = max(Msel, Isel);
                             const bool b = v > cbest;  // the smallest row wins a tie
                             cbest = b ? v : cbest;
@@ -258,7 +264,7 @@ __global__ __launch_bounds__(64) void ef_fill_long_kernel(
                     }
                 }
             }
-            if constexpr (kLocal) {
+            if constexpr (kEveryM) {
                 // a later chunk holds larger columns but starts over at row 1:
                 // it wins with a larger value, or the same value in a smaller row
                 const bool take = cbest > best || (cbest == best && cbest > 0 && cbest_i < best_i);

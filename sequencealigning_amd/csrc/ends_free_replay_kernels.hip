@@ -33,9 +33,10 @@ static_assert(kEfTileRowBytes == kLanes * kCols / 2, "a tile row holds a chunk's
 // columns of chunk c = (j - 1) / 1024.
 //   row r0         the checkpoint row (P(r0, j), D(r0 + 1, j)); row 0's formulas for r0 = 0
 //   column c0      the kept column c - 1 (P(r, c0), I(r, c0 + 1)), rows r0 + 1 .. i;
-//                  the chunk-0 constants for c = 0
+//                  the chunk-0 constants for c = 0 (extend: o + (r0 + rr) e)
 //   P(r0, col0)    a lane's first diagonal: the checkpoint's cell left of its
-//                  columns; lane 0 takes the kept column's row r0, or 0 in column 0
+//                  columns; lane 0 takes the kept column's row r0, or column 0's
+//                  P(r0, 0): 0, but extend's o + r0 e
 // The db and the column come through the chunked fill's refill: 64 rows ahead
 // in a register, the db's live rows in a 128-byte LDS ring.
 // kSub: as the chunked fill's (the block `sub` in LDS, symbols in qc and the ring).
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
     const uint8_t *__restrict__ ds, EfScoring sc, uint8_t *__restrict__ area, uint32_t R,
     const EfWalkState *__restrict__ state, const uint8_t *__restrict__ sub) {
     constexpr int K = kCols;
-    constexpr bool kLocal = kMode == SALN_MODE_LOCAL;
+    constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kExtend = kMode == SALN_MODE_EXTEND;
     __shared__ uint8_t ring[kRing];
     const uint8_t *ef_sub = ef_sub_stage<kSub>(sub);
     const uint32_t gi = blockIdx.x;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
             Hp[k] = v.x;
             Dn[k] = v.y;
         }
-        hd = lane > 0 ? cp[lane * K - 1].x : c > 0 ? col[r0 - 1].x : 0;
+        hd = lane > 0 ? cp[lane * K - 1].x : c > 0 ? col[r0 - 1].x : kExtend ? o + (int32_t)r0 * e : 0;
     }
     int32_t pubF = kEfNeg, pubH = kEfNeg;
     EfBest unused = ef_best_row0<kMode>(lq, o, e);  // the tile needs no end cell
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(64) void ef_tile_fill_kernel(
             const int s = t - t0;
             const int rr = t - lane + 1;  // the row inside the tile, 1 .. nrows
             const uint32_t dch = ring[(uint32_t)(t - lane) & (kRing - 1)];  // d[r0 + rr - 1]
-            int32_t bH = 0, bF = kLocal ? kEfNeg : o + e;  // column 0, as the fills have it
+            // column 0, as the fills have it; extend's row of lane 0 is r0 + rr = r0 + t + 1
+            int32_t bH = kExtend ? o + ((int32_t)r0 + t + 1) * e : 0, bF = kLocal || kExtend ? kEfNeg : o + e;
             if (c > 0) {
                 bH = __builtin_amdgcn_readlane(bcur.x, s);
                 bF = __builtin_amdgcn_readlane(bcur.y, s);
@@ -143,6 +145,7 @@ __global__ __launch_bounds__(64) void ef_tile_walk_kernel(
     const uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results,
     uint32_t *__restrict__ words, uint32_t *__restrict__ lens, EfWalkState *__restrict__ state) {
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
+    constexpr bool kExtend = kMode == SALN_MODE_EXTEND;
     const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
     if (gi >= count) return;
     const EfPair p = pairs[gi];
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(64) void ef_tile_walk_kernel(
         st = end_state[p.out] & 1u;  // 0 M, 1 I, 2 D
         n = run = op = 0;
         pend = kEfPendNone;
-        if ((kLocal || kOverlap) && res.score <= 0) i = j = 0;
+        if ((kLocal || kOverlap || kExtend) && res.score <= 0) i = j = 0;
         // overlap: the end state is the end cell's own code
         if (kOverlap && i > 0 && j > 0) pend = kEfPendArg;
     } else {
@@ -213,12 +216,17 @@ __global__ __launch_bounds__(64) void ef_tile_walk_kernel(
             pend = kEfPendNone;
         }
         if (j == 0) {
+            if constexpr (kExtend) {
+                // column 0 above the origin is one deletion run; no code is read
+                emit(SALN_CIGAR_D, i);
+                i = 0;
+            }
             done = true;
             break;
         }
         if (i == 0) {
-            // row 0.  Overlap: a free start.  Semi-global: the rest of the
-            // query is one insertion.  (Local never stands here.)
+            // row 0.  Overlap: a free start.  Semi-global and extend: the rest
+            // of the query is one insertion.  (Local never stands here.)
             if constexpr (!kOverlap) {
                 if (!kLocal) emit(SALN_CIGAR_I, j);
                 j = 0;
@@ -235,7 +243,7 @@ __global__ __launch_bounds__(64) void ef_tile_walk_kernel(
                     done = true;
                     break;
                 }
-                st = 1;  // semi-global row 0 is I; column 0 ends the loop
+                st = 1;  // semi-global and extend: row 0 is I; column 0 ends the loop
                 continue;
             }
             pend = kEfPendArg;

@@ -1,5 +1,5 @@
-"""Ends-free affine-gap alignment: local, semi-global and overlap — a
-separately labelled engine, NOT reference parity.
+"""Ends-free affine-gap alignment: local, semi-global, overlap and extension —
+a separately labelled engine, NOT reference parity.
 
 The reference only declares these modes (``ScoreTensor::Local`` /
 ``::SemiGlobal`` carry empty comments, needleman_wunsch_affine.rs:238-239,
@@ -18,10 +18,18 @@ against a db base; the db is the reference sequence).
   A suffix of one sequence against a prefix of the other, or one sequence
   inside the other; no overlap with a positive score gives the empty
   alignment (score 0, no words, coordinates 0).
+* ``EXTEND`` (8, this engine's own as well): extension alignment, the gapped
+  extension step of seed-and-extend.  The alignment is pinned at the origin
+  (both sequences' first bytes, the anchor) and free at its end: it may stop
+  at any cell, with no charge for what lies behind the stop.  Column 0 is a
+  deletion run and row 0 an insertion run, so an alignment may begin with
+  either.  No prefix pair with a positive score gives the empty alignment
+  (score 0, no words, coordinates 0).  ``extend_align(..., direction="left")``
+  extends leftwards from an anchor at the sequences' ends.
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
-include/saln.h and DESIGN.md; the checkers are tests/ends_free_model.py and
-tests/overlap_model.py.
+include/saln.h and DESIGN.md; the checkers are tests/ends_free_model.py,
+tests/overlap_model.py and tests/extend_model.py.
 
 ``ends_free_align_batch`` and its one-pair forms take a query of at most
 1,024 columns and a db of at most 65,000 rows.  ``ends_free_align_long_batch``,
@@ -57,6 +65,7 @@ DEFAULT_SCORING = (5, -4, -8, -6)
 TRACE_CAP = _lib.TRACE_CAP    # per-pair status: trace codes larger than the whole budget
 MAX_QUERY = 1024              # longest query (columns); saln_ends_free_pair_geometry
 OVERLAP = 4                   # SALN_MODE_OVERLAP: a mode value, not a records.Mode member
+EXTEND = 8                    # SALN_MODE_EXTEND: likewise
 
 
 class SubstitutionMatrix:
@@ -242,7 +251,8 @@ def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar,
 
 def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace_budget: int = 0,
                           cigar: bool = True, device: int = 0):
-    """Local, semi-global or overlap (mode=OVERLAP) alignment of a batch.
+    """Local, semi-global, overlap (mode=OVERLAP) or extension (mode=EXTEND)
+    alignment of a batch.
     pairs: None (all-vs-all, db
     outer / query inner) or (n, 2) (query index, db index).  Returns (results,
     cigars): results is a structured array (score, status, q_begin, q_end,
@@ -295,6 +305,46 @@ def overlap_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: in
     each range touching an end of its sequence; score 0 and no words when no
     overlap scores above 0."""
     return _one(seq1, seq2, OVERLAP, scoring, trace_budget, device)
+
+
+def _extend(seq1, seq2, direction, scoring, trace_budget, device, **kw):
+    if direction == "right":
+        return _one(seq1, seq2, EXTEND, scoring, trace_budget, device, **kw)
+    if direction != "left":
+        raise ValueError(f"extend_align: direction {direction!r} is neither 'right' nor 'left'")
+    q, d = bytes(seq1), bytes(seq2)
+    rec, cigar = _one(q[::-1], d[::-1], EXTEND, scoring, trace_budget, device, **kw)
+    rec = rec.copy()
+    rec["q_begin"], rec["q_end"] = len(q) - int(rec["q_end"]), len(q)
+    rec["db_begin"], rec["db_end"] = len(d) - int(rec["db_end"]), len(d)
+    return rec, list(cigar)[::-1]
+
+
+def extend_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
+                 direction: str = "right"):
+    """(result record, cigar) of the best extension of seq1 (query) and seq2
+    (db) from an anchor: the alignment of a prefix seq1[:q_end] with a prefix
+    seq2[:db_end] that scores highest, q_begin = db_begin = 0; score 0 and no
+    words when no such pair scores above 0.
+
+    direction="left" extends leftwards from an anchor at the sequences' ends:
+    the same kernels run on both sequences reversed, the CIGAR comes back
+    reversed (so it reads left to right along the sequences as given), and
+    the coordinates are counted on the sequences as given, from their right
+    ends: with (q_end', db_end') the end cell of the reversed run,
+    q_begin = len(seq1) - q_end', q_end = len(seq1), db_begin = len(seq2) -
+    db_end', db_end = len(seq2); the alignment is seq1[q_begin:] against
+    seq2[db_begin:], and the empty one has q_begin = q_end = len(seq1).  A
+    SubstitutionMatrix is not transposed by it: its rows stay the db's
+    symbols.  alignment_score takes the result of either direction."""
+    return _extend(seq1, seq2, direction, scoring, trace_budget, device)
+
+
+def extend_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
+                      direction: str = "right", replay: bool = False):
+    """extend_align for sequences of any length (ends_free_align_long_batch)."""
+    return _extend(seq1, seq2, direction, scoring, trace_budget, device,
+                   batch=ends_free_align_long_batch, replay=replay)
 
 
 def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
