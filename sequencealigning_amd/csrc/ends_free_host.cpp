@@ -2,8 +2,8 @@
 // semi-global, overlap and extension affine-gap alignment.  Not a
 // reference-parity path - the reference only declares the first two modes
 // (needleman_wunsch_affine.rs:238-239, :331-332, :433-434) and has no overlap
-// and no extension; the checkers are the plain models tests/ends_free_model.py,
-// tests/overlap_model.py and tests/extend_model.py.
+// and no extension; the checker of the four modes is the plain model
+// tests/ends_free_model.py.
 //
 // A batch's pairs are grouped by query class (ef_class_of) and, within a
 // class, ordered by falling db length and cut where the length's power-of-two

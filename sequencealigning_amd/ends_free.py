@@ -28,8 +28,8 @@ against a db base; the db is the reference sequence).
   extends leftwards from an anchor at the sequences' ends.
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
-include/saln.h and DESIGN.md; the checkers are tests/ends_free_model.py,
-tests/overlap_model.py and tests/extend_model.py.
+include/saln.h and DESIGN.md; the checker of the four modes under both kinds
+of scoring is tests/ends_free_model.py.
 
 ``ends_free_align_batch`` and its one-pair forms take a query of at most
 1,024 columns and a db of at most 65,000 rows.  ``ends_free_align_long_batch``,

@@ -1,9 +1,12 @@
 """Pins tests/ends_free_model.py (the checker of the ends-free engine) against
 brute-force enumeration written here, independent of the model: every
 alignment of every substring pair, gaps opening from M only (an I run and a D
-run are never adjacent).  CPU only."""
+run are never adjacent); and its canonical choices against
+tests/golden/ends_free_model_pins.json.  CPU only."""
 import functools
 import itertools
+import json
+import os
 import random
 
 import pytest
@@ -11,7 +14,7 @@ import pytest
 import ends_free_model as model
 
 SCHEMES = [(5, -4, -8, -6), (1, -1, 0, -1), (2, -3, -5, -2)]
-MODES = [model.LOCAL, model.SEMI_GLOBAL]
+MODES = [model.LOCAL, model.SEMI_GLOBAL, model.OVERLAP, model.EXTEND]
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,6 +70,15 @@ def brute(q, d, mode, scheme):
             for b0, b1 in itertools.combinations(range(len(d) + 1), 2):
                 best = max(best, _best_global(q[a0:a1], d[b0:b1], scheme))
         return best
+    if mode == model.OVERLAP:      # from row 0 or column 0 to row m or column n, or nothing at all
+        n, m = len(q), len(d)
+        return max([0] + [_best_global(q[a0:a1], d[b0:b1], scheme)
+                          for a0 in range(n + 1) for a1 in range(a0, n + 1)
+                          for b0 in range(m + 1) for b1 in range(b0, m + 1)
+                          if (a0 == 0 or b0 == 0) and (a1 == n or b1 == m)])
+    if mode == model.EXTEND:       # a prefix of d with a prefix of q, or nothing at all
+        return max([0] + [_best_global(q[:j], d[:i], scheme)
+                          for i in range(len(d) + 1) for j in range(len(q) + 1)])
     best = None
     for b0 in range(len(d) + 1):
         for b1 in range(b0, len(d) + 1):
@@ -82,6 +94,14 @@ def check_alignment(q, d, mode, scheme, a):
     assert 0 <= a.q_begin <= a.q_end <= len(q) and 0 <= a.db_begin <= a.db_end <= len(d)
     if mode == model.SEMI_GLOBAL:
         assert (a.q_begin, a.q_end) == (0, len(q))
+    elif a.score == 0:
+        assert a.cigar == [] and a.record() == (0, 0, 0, 0, 0, 0, 0, 0)
+    elif mode == model.OVERLAP:
+        assert a.q_begin == 0 or a.db_begin == 0
+        assert a.q_end == len(q) or a.db_end == len(d)
+    elif mode == model.EXTEND:
+        assert (a.q_begin, a.db_begin) == (0, 0)
+        assert a.cigar[-1][1] in "=X", "ending in a gap is never better"
     j, i = a.q_begin, a.db_begin
     total, prev = 0, None
     for n, op in a.cigar:
@@ -184,3 +204,49 @@ def test_a_long_pair_is_quick():
     for mode in MODES:
         check_alignment(q, d, mode, model.DEFAULT_SCORING, model.align(q, d, mode))
     assert time.perf_counter() - t < 5.0
+
+
+# ------------------------------------------------------------------ the pins
+def _pins():
+    """(q, d, mode, scoring, record, CIGAR string) of every entry."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "golden", "ends_free_model_pins.json")) as f:
+        for entry in json.load(f)["scorings"]:
+            sc = entry["scoring"]
+            sc = tuple(sc) if isinstance(sc, list) else model.matrix_scoring(
+                sc["alphabet"].encode(), sc["table"], sc["o"], sc["e"])
+            for mode in MODES:
+                for (q, d), (record, cigar) in zip(entry["pairs"], entry["expected"][str(mode)]):
+                    yield q.encode(), d.encode(), mode, sc, tuple(record), cigar
+
+
+def test_pins():
+    """The model gives the records and CIGARs the four models it replaced
+    gave (the fixture was written from them), with and without the walk and
+    with rolling rows; and the fixture holds the cases that make this a pin of
+    the tie rules.  A CIGAR that starts with 'I' or 'D' is asked of every mode
+    whose definition admits one: a local alignment starts with '=' or 'X',
+    and semi-global's D(i,0) is -infinity, so those are asserted absent."""
+    first = {mode: set() for mode in MODES}
+    overlap_ties = local_ties = entries = 0
+    for q, d, mode, sc, record, cigar in _pins():
+        entries += 1
+        a = model.align(q, d, mode, sc)
+        assert (a.record(), "".join(f"{k}{op}" for k, op in a.cigar)) == (record, cigar), (q, d, mode)
+        b = model.align(q, d, mode, sc, walk=False)
+        ends = (a.score, -1, a.q_end, -1, a.db_end)
+        if mode != model.SEMI_GLOBAL and a.score == 0:
+            ends = (0, -1, 0, -1, 0)
+        assert (b.score, b.q_begin, b.q_end, b.db_begin, b.db_end) == ends and b.cigar == []
+        assert model.linear_ends(q, d, mode, sc) == (a.score, a.q_end, a.db_end), (q, d, mode)
+        first[mode].add(cigar.lstrip("0123456789")[:1])       # "" for the empty alignment
+        if mode == model.OVERLAP and a.score:
+            info = model.end_info(q, d, sc)
+            overlap_ties += len(info["col_ties"]) + len(info["row_ties"]) > 1
+        if mode == model.LOCAL:
+            local_ties += model.tied_ends(q, d, mode, sc)[0] > 1
+    assert entries == 5 * 40 * 4
+    assert "" in first[model.LOCAL] and not first[model.LOCAL] & {"I", "D"}
+    assert "I" in first[model.SEMI_GLOBAL] and "D" not in first[model.SEMI_GLOBAL]
+    assert first[model.OVERLAP] >= {"", "I", "D"} and first[model.EXTEND] >= {"", "I", "D"}
+    assert overlap_ties >= 10 and local_ties >= 10

@@ -1,7 +1,7 @@
 """CPU, no device: the host-only side of the ends-free replay traceback
 (saln_ends_free_replay_bytes, option ends_free.tile_rows) and the inputs of
 test_ends_free_replay_gpu.py with their preconditions, asserted from the plain
-models: which tile edge each constructed path crosses, and how.
+model: which tile edge each constructed path crosses, and how.
 
 A tile is a 1,024-column chunk times a block of R db rows; the GPU file runs
 these inputs at R = 64, so "column 1,024" is a chunk edge and "row 64" a
@@ -12,10 +12,9 @@ import numpy as np
 import pytest
 
 import ends_free_model as model
-import overlap_model as omodel
 import test_ends_free_long as cpu
 
-LOCAL, SEMI, OVERLAP = model.LOCAL, model.SEMI_GLOBAL, omodel.OVERLAP
+LOCAL, SEMI, OVERLAP = model.LOCAL, model.SEMI_GLOBAL, model.OVERLAP
 MODES = [LOCAL, SEMI, OVERLAP]
 TILE_ROWS = (64, 128, 256, 512, 1024)
 CHUNK = 1024
@@ -26,8 +25,8 @@ def _rand(rng, n, alphabet=b"ACGT"):
 
 
 def align(q, d, mode, scheme=None):
-    """The plain model of the mode."""
-    return omodel.align(q, d, scheme) if mode == OVERLAP else model.align(q, d, mode, scheme)
+    """The plain model."""
+    return model.align(q, d, mode, scheme)
 
 
 def components(n, m, R):

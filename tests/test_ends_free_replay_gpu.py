@@ -3,7 +3,7 @@
 semi-global and overlap.  Every comparison is exact on the whole record and
 every word, against two references: the long entry point with its default
 budget (the full trace, GPU against GPU) and, wherever the db has at most 200
-rows (or the query 5 columns), the plain models.  The inputs and their
+rows (or the query 5 columns), the plain model.  The inputs and their
 preconditions (which tile edge a path crosses, and how) are in
 test_ends_free_replay.py (no device); a tile there is 1,024 columns x 64 rows,
 set here through the option ends_free.tile_rows."""

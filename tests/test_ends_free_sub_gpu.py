@@ -1,7 +1,7 @@
 """GPU: the ends-free engine under a substitution matrix (the kSub instances
 of ends_free_kernels.hip through saln_ends_free_sub_*), local, semi-global and
 overlap.  Every comparison is exact against the plain model
-(ends_free_sub_model.py): the whole result record and the CIGAR, word for
+(ends_free_model.py): the whole result record and the CIGAR, word for
 word; and alignment_score of every returned alignment is its score."""
 import ctypes
 import random
@@ -9,7 +9,7 @@ import random
 import numpy as np
 import pytest
 
-import ends_free_sub_model as model
+import ends_free_model as model
 
 LOCAL, SEMI, OVERLAP = model.LOCAL, model.SEMI_GLOBAL, model.OVERLAP
 MODES = [LOCAL, SEMI, OVERLAP]

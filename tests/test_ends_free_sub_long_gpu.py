@@ -2,14 +2,14 @@
 substitution matrix (the kSub instances of ends_free_long_kernels.hip and
 ends_free_replay_kernels.hip through saln_ends_free_sub_long_align_batch and
 saln_ends_free_sub_replay_align_batch).  Every comparison is exact against the
-plain model (ends_free_sub_model.py); the inputs' preconditions (each path
+plain model (ends_free_model.py); the inputs' preconditions (each path
 crosses a chunk edge and a tile edge) are asserted from the model first, and
 without a device in test_the_paths_cross_chunk_and_tile_edges."""
 import random
 
 import pytest
 
-import ends_free_sub_model as model
+import ends_free_model as model
 import test_ends_free_sub_gpu as sg
 
 LOCAL, SEMI, OVERLAP = model.LOCAL, model.SEMI_GLOBAL, model.OVERLAP

@@ -1,17 +1,14 @@
-"""Pins tests/ends_free_sub_model.py (the checker of the ends-free engine under
-a substitution matrix) against brute-force enumeration written here,
-independent of the model, and against the two scalar models
-(ends_free_model.py, overlap_model.py) under a match / mismatch matrix.
-CPU only."""
+"""Pins tests/ends_free_model.py under a substitution matrix (the checker of
+saln_ends_free_sub_*) against brute-force enumeration written here,
+independent of the model, and its scalar scoring against the equivalent
+match / mismatch matrix.  CPU only."""
 import functools
 import itertools
 import random
 
 import pytest
 
-import ends_free_model as ef_model
-import ends_free_sub_model as model
-import overlap_model as ov_model
+import ends_free_model as model
 
 MODES = [model.LOCAL, model.SEMI_GLOBAL, model.OVERLAP]
 
@@ -196,33 +193,26 @@ def test_a_transposed_lookup_would_show():
     assert model.align(b"G", b"G", model.SEMI_GLOBAL, sc).score == -1
 
 
-# ------------------------------------------------------------------ the scalar models
+# ------------------------------------------------------------------ the scalar schemes
 SCHEMES = [(5, -4, -8, -6), (1, -1, 0, -1), (2, -3, -5, -2)]
 
 
-def _same(a, b):
-    return a.record() == b.record() and a.cigar == b.cigar
-
-
 @pytest.mark.parametrize("scheme", SCHEMES)
-def test_match_mismatch_matrix_equals_the_scalar_models(scheme):
+def test_scalar_scoring_equals_the_match_mismatch_matrix(scheme):
     ma, mi, o, e = scheme
     table = [[ma if a == b else mi for b in range(4)] for a in range(4)]
-    for sc in (model.scalar_scoring(*scheme), model.matrix_scoring(b"ACGT", table, o, e)):
-        rng = random.Random(0xACE + ma)
-        for k in range(150):
-            q = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 40)))
-            d = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 60)))
-            if k % 3 == 0 and len(q) > 8:      # a planted overlap: a query suffix on a db prefix
-                d = q[-8:] + d
+    scalar, matrix = model.scalar_scoring(*scheme), model.matrix_scoring(b"ACGT", table, o, e)
+    rng = random.Random(0xACE + ma)
+    for k in range(150):
+        q = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 40)))
+        d = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 60)))
+        if k % 3 == 0 and len(q) > 8:      # a planted overlap: a query suffix on a db prefix
+            d = q[-8:] + d
+        for mode in MODES + [model.EXTEND]:
             for walk in (True, False):
-                assert _same(model.align(q, d, model.LOCAL, sc, walk=walk),
-                             ef_model.align(q, d, ef_model.LOCAL, scheme, walk=walk)), (q, d)
-                assert _same(model.align(q, d, model.SEMI_GLOBAL, sc, walk=walk),
-                             ef_model.align(q, d, ef_model.SEMI_GLOBAL, scheme, walk=walk)), (q, d)
-                assert _same(model.align(q, d, model.OVERLAP, sc, walk=walk),
-                             ov_model.align(q, d, scheme, walk=walk)), (q, d)
-            assert model.linear_ends(q, d, model.OVERLAP, sc) == ov_model.linear_ends(q, d, scheme)
+                a, b, c = (model.align(q, d, mode, sc, walk=walk) for sc in (scheme, scalar, matrix))
+                assert a.record() == b.record() == c.record() and a.cigar == b.cigar == c.cigar, (q, d, mode)
+            assert model.linear_ends(q, d, mode, scalar) == model.linear_ends(q, d, mode, matrix)
 
 
 def test_case_insensitive_and_unknown():

@@ -1,7 +1,7 @@
 """GPU: the ends-free engine's extension mode, SALN_MODE_EXTEND (the kMode ==
 SALN_MODE_EXTEND instances of ends_free_kernels.hip): pinned at the origin,
 free at its end.  Every comparison is exact against the plain model
-(extend_model.py): the whole result record and the CIGAR, word for word, with
+(ends_free_model.py): the whole result record and the CIGAR, word for word, with
 CIGAR, score only and through EndsFreePlan; alignment_score of every returned
 alignment is its score."""
 import random
@@ -9,7 +9,7 @@ import random
 import numpy as np
 import pytest
 
-import extend_model as model
+import ends_free_model as model
 
 EXTEND = model.EXTEND
 DEFAULT = (5, -4, -8, -6)
@@ -59,7 +59,7 @@ def anchored(rng, q, length, letters):
 
 
 def expect(q, d, msc, walk=True):
-    a = model.align(q, d, msc, walk=walk)
+    a = model.align(q, d, EXTEND, msc, walk=walk)
     return a.record(), model.cigar_words(a.cigar)
 
 
@@ -160,7 +160,7 @@ def test_leading_deletion(saln):
     qs, ds = [s], [b"N" * g + s + tail for g in gaps]     # N occurs in neither s nor the tail
     pairs = [(0, k) for k in range(len(gaps))]
     for g, d in zip(gaps, ds):
-        a = model.align(s, d, msc)
+        a = model.align(s, d, EXTEND, msc)
         assert a.cigar == [(g, "D"), (200, "=")] and a.score == 1000 - 8 - 6 * g
     assert expect(s, ds[2], msc)[0][:6] == (608, 0, 0, 200, 0, 264)
     res, cig = compare(saln, qs, ds, pairs, DEFAULT, msc)
@@ -242,7 +242,7 @@ def test_direction_left(saln, name):
     for n, m in ((40, 60), (300, 90), (11, 11), (5, 0)):
         q = rand_seq(rng, n, letters)
         d = anchored(rng, q[::-1], m, letters)[::-1]       # related at the right ends
-        want = model.left_coords(model.align(q[::-1], d[::-1], msc), n, m)
+        want = model.left_coords(model.align(q[::-1], d[::-1], EXTEND, msc), n, m)
         rec, cigar = saln.extend_align(q, d, scoring=sc, direction="left")
         assert tuple(int(v) for v in rec) == want.record() and cigar == want.cigar
         assert saln.alignment_score(q, d, (rec, cigar), sc) == want.score
@@ -262,7 +262,7 @@ def test_the_longest_db_of_the_class_fills(saln):
     ds = [anchored(rng, qs[1], 400, letters) + rand_seq(rng, 64600, letters)]
     res, _ = saln.ends_free_align_batch(qs, ds, None, mode=EXTEND, scoring=sc, cigar=False)
     for k in range(2):
-        score, q_end, db_end = model.linear_ends(qs[k], ds[0], msc)
+        score, q_end, db_end = model.linear_ends(qs[k], ds[0], EXTEND, msc)
         assert tuple(int(v) for v in res[k]) == (score, 0, -1, q_end, -1, db_end, 0, 0)
     assert int(res["score"][1]) > 500
 

@@ -1,7 +1,7 @@
 """GPU: extension mode (SALN_MODE_EXTEND) through the chunked fill with the
 full trace and through the tiled replay at ends_free.tile_rows = 64
 (ends_free_long_kernels.hip, ends_free_replay_kernels.hip).  Both equal the
-plain model (extend_model.py), record for record and word for word, and each
+plain model (ends_free_model.py), record for record and word for word, and each
 other; the inputs' preconditions (a path over a chunk edge and a tile edge,
 column 0 over tile edges, row 0 past a chunk edge) are asserted from the model
 first, and without a device in test_the_paths_are_what_the_cases_need."""
@@ -9,7 +9,7 @@ import random
 
 import pytest
 
-import extend_model as model
+import ends_free_model as model
 import test_extend_gpu as eg
 
 EXTEND = model.EXTEND
@@ -85,7 +85,7 @@ def expected(key):
         _, msc, letters = scoring(None, key)
         for q, d in crossing_pairs(letters):
             path = []
-            a = model.align(q, d, msc, path=path)
+            a = model.align(q, d, EXTEND, msc, path=path)
             assert path[-1] == (0, 0) and a.score > 0
             cells = [(i, j) for i, j in path if i >= 1 and j >= 1]
             chunks = [(j - 1) // CHUNK for _, j in cells]
@@ -98,13 +98,13 @@ def expected(key):
     elif key == "deletions":
         msc = model.scalar_scoring(*eg.DEFAULT)
         for (q, d), g in zip(border_pairs()[0], (64, 65, 130)):
-            a = model.align(q, d, msc)
+            a = model.align(q, d, EXTEND, msc)
             assert a.cigar == [(g, "D"), (1100, "=")] and a.score == 5500 - 8 - 6 * g
             out.append((q, d, a.record(), model.cigar_words(a.cigar)))
     else:
         msc = model.scalar_scoring(*ROW0)
         q, d = border_pairs()[1]
-        a = model.align(q, d, msc)
+        a = model.align(q, d, EXTEND, msc)
         assert a.cigar == [(1030, "I"), (300, "=")] and a.record()[:6] == (468, 0, 0, 1330, 0, 300)
         out.append((q, d, a.record(), model.cigar_words(a.cigar)))
     _expected[key] = out
@@ -166,6 +166,6 @@ def test_db_above_the_class_limit_score_only(saln):
     d = eg.anchored(rng, q, 60, letters) + eg.rand_seq(rng, 64941, letters)
     assert saln.ends_free.pair_path_long(40, 65001) == (1, 1)
     res, cig = saln.ends_free.ends_free_align_long_batch([q], [d], mode=EXTEND, scoring=sc, cigar=False)
-    score, q_end, db_end = model.linear_ends(q, d, msc)
+    score, q_end, db_end = model.linear_ends(q, d, EXTEND, msc)
     assert tuple(int(v) for v in res[0]) == (score, 0, -1, q_end, -1, db_end, 0, 0) and cig[0] == []
     assert score > 0

@@ -1,5 +1,5 @@
-"""Pins tests/extend_model.py (the checker of the ends-free engine's extension
-mode, SALN_MODE_EXTEND) against brute-force enumeration, against the local
+"""Pins tests/ends_free_model.py's EXTEND (the checker of the ends-free engine's
+extension mode, SALN_MODE_EXTEND) against brute-force enumeration, against the local
 model, and the mode's constant against the header.  CPU only."""
 import itertools
 import os
@@ -8,8 +8,7 @@ import re
 
 import pytest
 
-import ends_free_sub_model as sub_model
-import extend_model as model
+import ends_free_model as model
 from test_ends_free_sub_model import ALPHABET3, TABLE3, _best_global
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,12 +58,12 @@ def check_alignment(q, d, sc, a):
 
 
 def _check_pair(q, d, sc, cache):
-    a = model.align(q, d, sc)
+    a = model.align(q, d, model.EXTEND, sc)
     assert a.score == brute(q, d, sc, cache), (q, d)
     check_alignment(q, d, sc, a)
-    b = model.align(q, d, sc, walk=False)
+    b = model.align(q, d, model.EXTEND, sc, walk=False)
     assert b.record()[:6] == ((a.score, 0, -1, a.q_end, -1, a.db_end)) and b.cigar == []
-    assert model.linear_ends(q, d, sc) == (a.score, a.q_end, a.db_end), (q, d)
+    assert model.linear_ends(q, d, model.EXTEND, sc) == (a.score, a.q_end, a.db_end), (q, d)
 
 
 @pytest.mark.parametrize("gaps", GAPS)
@@ -76,7 +75,8 @@ def test_every_small_pair_over_three_symbols(gaps):
     for q in strings:
         for d in strings:
             _check_pair(q, d, sc, cache)
-            seen.add(model.align(q, d, sc).cigar[0][1] if model.align(q, d, sc).score else "")
+            a = model.align(q, d, model.EXTEND, sc)
+            seen.add(a.cigar[0][1] if a.score else "")
     assert {"", "=", "X", "I", "D"} <= seen      # alignments that begin with either border gap
 
 
@@ -102,8 +102,8 @@ def test_between_nothing_and_local(scheme):
         d = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 50)))
         if k % 2 and q:
             d = q[:rng.randint(1, len(q))] + d       # a shared prefix: the anchor
-        a = model.align(q, d, sc)
-        loc = sub_model.align(q, d, sub_model.LOCAL, sc)
+        a = model.align(q, d, model.EXTEND, sc)
+        loc = model.align(q, d, model.LOCAL, sc)
         check_alignment(q, d, sc, a)
         assert 0 <= a.score <= loc.score
         below += a.score < loc.score
@@ -117,17 +117,17 @@ def test_hand_written_cases():
     sc = model.scalar_scoring(5, -4, -8, -6)
     s = b"ACGTTGCAAGTCCATGACGT"
     # a leading deletion, a leading insertion: the border runs
-    a = model.align(s, b"N" + s, sc)
+    a = model.align(s, b"N" + s, model.EXTEND, sc)
     assert (a.score, a.cigar) == (100 - 14, [(1, "D"), (20, "=")]) and (a.q_end, a.db_end) == (20, 21)
-    a = model.align(b"NN" + s, s, sc)
+    a = model.align(b"NN" + s, s, model.EXTEND, sc)
     assert (a.score, a.cigar) == (100 - 20, [(2, "I"), (20, "=")]) and (a.q_end, a.db_end) == (22, 20)
     # the anchor costs more than it earns: nothing, where local finds the match
-    a = model.align(s[:4], b"NNN" + s[:4], sc)
+    a = model.align(s[:4], b"NNN" + s[:4], model.EXTEND, sc)
     assert a.record() == (0, 0, 0, 0, 0, 0, 0, 0)
-    assert sub_model.align(s[:4], b"NNN" + s[:4], sub_model.LOCAL, sc).score == 20
+    assert model.align(s[:4], b"NNN" + s[:4], model.LOCAL, sc).score == 20
     # the alignment stops where the sequences part
     path = []
-    a = model.align(s + b"AAAAAA", s + b"CCCCCCCC", sc, path=path)
+    a = model.align(s + b"AAAAAA", s + b"CCCCCCCC", model.EXTEND, sc, path=path)
     assert (a.score, a.q_end, a.db_end, a.cigar) == (100, 20, 20, [(20, "=")])
     assert path[0] == (20, 20) and path[-1] == (0, 0) and len(path) == 21
 
@@ -136,19 +136,19 @@ def test_direction_left_coordinates():
     """direction="left": the model on the reversed sequences, mapped back."""
     sc = model.scalar_scoring(5, -4, -8, -6)
     q, d = b"TTTTTCACCA", b"GGGACCA"        # the anchor is at the right ends
-    a = model.align(q[::-1], d[::-1], sc)
+    a = model.align(q[::-1], d[::-1], model.EXTEND, sc)
     assert (a.score, a.q_end, a.db_end, a.cigar) == (20, 4, 4, [(4, "=")])
     left = model.left_coords(a, len(q), len(d))
     assert left.record()[:6] == (20, 0, 6, 10, 3, 7) and left.cigar == [(4, "=")]
     assert q[left.q_begin:left.q_end] == d[left.db_begin:left.db_end] == b"ACCA"
     # an asymmetric alignment: the reversed CIGAR reads left to right
     q, d = b"GGACGTACGTAC", b"ACGTTTACGTAC"
-    a = model.align(q[::-1], d[::-1], model.scalar_scoring(5, -4, -2, -1))
+    a = model.align(q[::-1], d[::-1], model.EXTEND, model.scalar_scoring(5, -4, -2, -1))
     left = model.left_coords(a, len(q), len(d))
     assert left.cigar == a.cigar[::-1] and (left.q_end, left.db_end) == (12, 12)
     assert (left.q_begin, left.db_begin) == (12 - a.q_end, 12 - a.db_end)
     # the empty alignment sits at the right ends
-    e = model.left_coords(model.align(b"AAAA", b"CCCC", sc), 4, 4)
+    e = model.left_coords(model.align(b"AAAA", b"CCCC", model.EXTEND, sc), 4, 4)
     assert e.record()[:6] == (0, 0, 4, 4, 4, 4)
 
 
@@ -166,8 +166,8 @@ def test_alignment_score_takes_both_directions():
     from sequencealigning_amd import _lib
     sc = model.scalar_scoring(5, -4, -2, -1)
     q, d = b"GGACGTACGTAC", b"ACGTTTACGTAC"
-    for a, (qq, dd) in ((model.align(q, d, sc), (q, d)),
-                        (model.left_coords(model.align(q[::-1], d[::-1], sc), len(q), len(d)), (q, d))):
+    for a, (qq, dd) in ((model.align(q, d, model.EXTEND, sc), (q, d)),
+                        (model.left_coords(model.align(q[::-1], d[::-1], model.EXTEND, sc), len(q), len(d)), (q, d))):
         rec = np.zeros(1, _lib.ENDS_FREE_RESULT_DTYPE)[0]
         rec["score"], rec["q_begin"], rec["q_end"] = a.score, a.q_begin, a.q_end
         rec["db_begin"], rec["db_end"] = a.db_begin, a.db_end

@@ -1,7 +1,7 @@
 """GPU: the ends-free engine's overlap (dovetail) mode, SALN_MODE_OVERLAP = 4,
 through both fills (ends_free_kernels.hip, ends_free_long_kernels.hip), the
 walk, the batch code and the device-resident plan.  Every comparison is exact
-against the plain model (overlap_model.py): the whole result record and the
+against the plain model (ends_free_model.py): the whole result record and the
 CIGAR, word for word.  The inputs' preconditions are asserted from the model
 where the inputs are built."""
 import random
@@ -9,7 +9,7 @@ import random
 import numpy as np
 import pytest
 
-import overlap_model as model
+import ends_free_model as model
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +51,7 @@ def _model(q, d, scheme=None):
     key = (q, d, scheme)
     if key not in _expected:
         info = {}
-        _expected[key] = (model.align(q, d, scheme, info=info), info)
+        _expected[key] = (model.align(q, d, OVERLAP, scheme, info=info), info)
     return _expected[key]
 
 
@@ -336,14 +336,14 @@ def test_long_db_short_query(saln):
     q = acgt[rng.integers(0, 4, 100)].tobytes()
     d = acgt[rng.integers(0, 4, 65001 - 61)].tobytes() + b"N" + q[:60]
     assert saln.ends_free.pair_path_long(100, len(d)) == (1, 1)
-    want = model.linear_ends(q, d)
+    want = model.linear_ends(q, d, OVERLAP)
     assert want == (300, 60, 65001)
     res, cig = saln.ends_free_align_long_batch([q], [d], mode=OVERLAP)
     assert tuple(int(v) for v in res[0]) == (300, 0, 0, 60, 65001 - 60, 65001, 1, 0)
     assert cig[0] == [(60, "=")]
     # the query's suffix on the db's prefix: the last column, in row 70
     d = q[30:] + b"N" + acgt[rng.integers(0, 4, 65001 - 71)].tobytes()
-    assert model.linear_ends(q, d) == (350, 100, 70)
+    assert model.linear_ends(q, d, OVERLAP) == (350, 100, 70)
     res, cig = saln.ends_free_align_long_batch([q], [d], mode=OVERLAP)
     assert tuple(int(v) for v in res[0]) == (350, 0, 30, 100, 0, 70, 1, 0)
 

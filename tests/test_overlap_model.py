@@ -1,5 +1,5 @@
 """CPU, no device: the plain model of overlap (dovetail) alignment
-(overlap_model.py) against brute-force enumeration, its tie rules on hand
+(ends_free_model.py, OVERLAP) against brute-force enumeration, its tie rules on hand
 cases, its place between semi-global and local, and the host-only ABI the new
 mode must leave alone."""
 import itertools
@@ -8,8 +8,7 @@ import random
 import re
 from functools import lru_cache
 
-import ends_free_model as ef_model
-import overlap_model as model
+import ends_free_model as model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the engine's three test schemes and one whose mismatch is worse than o + e
@@ -88,18 +87,18 @@ def check_alignment(q, d, a, scheme):
 def _check_pair(q, d):
     counts = brute_counts(q, d)
     for scheme in SCHEMES:
-        a = model.align(q, d, scheme)
+        a = model.align(q, d, model.OVERLAP, scheme)
         assert a.score == brute_score(counts, scheme), (q, d, scheme)
         check_alignment(q, d, a, scheme)
-        b = model.align(q, d, scheme, walk=False)
+        b = model.align(q, d, model.OVERLAP, scheme, walk=False)
         want = (a.score, -1, a.q_end, -1, a.db_end) if a.score else (0, -1, 0, -1, 0)
         assert (b.score, b.q_begin, b.q_end, b.db_begin, b.db_end) == want and b.cigar == []
-        assert model.linear_ends(q, d, scheme) == (a.score, a.q_end, a.db_end), (q, d, scheme)
+        assert model.linear_ends(q, d, model.OVERLAP, scheme) == (a.score, a.q_end, a.db_end), (q, d, scheme)
         # between the engine's other modes: both semi-global end sets lie on
         # overlap's two borders, and a local alignment may drop any overhang
-        local = ef_model.align(q, d, ef_model.LOCAL, scheme, walk=False).score
-        semi_qd = ef_model.align(q, d, ef_model.SEMI_GLOBAL, scheme, walk=False).score
-        semi_dq = ef_model.align(d, q, ef_model.SEMI_GLOBAL, scheme, walk=False).score
+        local = model.align(q, d, model.LOCAL, scheme, walk=False).score
+        semi_qd = model.align(q, d, model.SEMI_GLOBAL, scheme, walk=False).score
+        semi_dq = model.align(d, q, model.SEMI_GLOBAL, scheme, walk=False).score
         assert max(semi_qd, semi_dq) <= a.score <= local, (q, d, scheme)
 
 
@@ -125,35 +124,35 @@ def test_harsh_mismatch_scheme_is_harsh():
 
 # ------------------------------------------------------------------ hand cases
 def test_dovetails_and_containments():
-    a = model.align(b"TTTTACGTA", b"ACGTACCCC")          # query suffix over db prefix
+    a = model.align(b"TTTTACGTA", b"ACGTACCCC", model.OVERLAP)          # query suffix over db prefix
     assert a.record() == (25, 0, 4, 9, 0, 5, 1, 0) and a.cigar == [(5, "=")]
-    a = model.align(b"ACGTACCCC", b"TTTTACGTA")          # db suffix over query prefix
+    a = model.align(b"ACGTACCCC", b"TTTTACGTA", model.OVERLAP)          # db suffix over query prefix
     assert a.record() == (25, 0, 0, 5, 4, 9, 1, 0)
-    a = model.align(b"ACGTAC", b"GGGACGTACGGG")          # the query inside the db
+    a = model.align(b"ACGTAC", b"GGGACGTACGGG", model.OVERLAP)          # the query inside the db
     assert a.record() == (30, 0, 0, 6, 3, 9, 1, 0)
-    a = model.align(b"GGGACGTACGGG", b"ACGTAC")          # the db inside the query
+    a = model.align(b"GGGACGTACGGG", b"ACGTAC", model.OVERLAP)          # the db inside the query
     assert a.record() == (30, 0, 3, 9, 0, 6, 1, 0)
-    a = model.align(b"ACGTACGT", b"ACGTACGT")
+    a = model.align(b"ACGTACGT", b"ACGTACGT", model.OVERLAP)
     assert a.record() == (40, 0, 0, 8, 0, 8, 1, 0)
     for q, d in ((b"AAAA", b"CCCCCC"), (b"", b"ACGT"), (b"ACGT", b""), (b"", b""), (b"A", b"C")):
-        assert model.align(q, d).record() == (0, 0, 0, 0, 0, 0, 0, 0)
-        assert model.align(q, d, walk=False).record() == (0, 0, -1, 0, -1, 0, 0, 0)
-    assert model.align(b"A", b"A").record() == (5, 0, 0, 1, 0, 1, 1, 0)
+        assert model.align(q, d, model.OVERLAP).record() == (0, 0, 0, 0, 0, 0, 0, 0)
+        assert model.align(q, d, model.OVERLAP, walk=False).record() == (0, 0, -1, 0, -1, 0, 0, 0)
+    assert model.align(b"A", b"A", model.OVERLAP).record() == (5, 0, 0, 1, 0, 1, 1, 0)
 
 
 def test_tie_rules():
     # a last-column cell above row m against a last-row cell: the smaller row
     info = model.end_info(b"ACTTTTAC", b"ACGGGGAC")
     assert info["col_ties"] == [2] and info["row_ties"] == [2]
-    assert model.align(b"ACTTTTAC", b"ACGGGGAC").record() == (10, 0, 6, 8, 0, 2, 1, 0)
+    assert model.align(b"ACTTTTAC", b"ACGGGGAC", model.OVERLAP).record() == (10, 0, 6, 8, 0, 2, 1, 0)
     # two last-row cells, one of them the corner: the smaller column
     info = model.end_info(b"ACTAC", b"AC")
     assert info["row_ties"] == [2, 5] and info["col_ties"] == [2]
-    assert model.align(b"ACTAC", b"AC").record() == (10, 0, 0, 2, 0, 2, 1, 0)
+    assert model.align(b"ACTAC", b"AC", model.OVERLAP).record() == (10, 0, 0, 2, 0, 2, 1, 0)
     # two last-column cells, one of them the corner: the smaller row
     info = model.end_info(b"AC", b"ACTAC")
     assert info["col_ties"] == [2, 5] and info["row_ties"] == [2]
-    assert model.align(b"AC", b"ACTAC").record() == (10, 0, 0, 2, 0, 2, 1, 0)
+    assert model.align(b"AC", b"ACTAC", model.OVERLAP).record() == (10, 0, 0, 2, 0, 2, 1, 0)
 
 
 def test_end_states_and_gap_exits():
@@ -168,7 +167,7 @@ def test_end_states_and_gap_exits():
         (b"AAA", b"CAC", "M", (3, 0, 2, 3, 0, 2, 2, 0), [(1, "D"), (1, "=")]),
     ]
     for q, d, st, rec, cigar in cases:
-        a = model.align(q, d, sc)
+        a = model.align(q, d, model.OVERLAP, sc)
         assert (model.end_info(q, d, sc)["st"], a.record(), a.cigar) == (st, rec, cigar), (q, d)
         check_alignment(q, d, a, sc)
         assert a.score == brute_score(brute_counts(q, d), sc)

@@ -18,42 +18,10 @@ Prints one JSON line.
 import argparse
 import ctypes as C
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-def _events_ms(fn, warmup, steps):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return ts
-
-
-def _wall_ms(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return ts
+from ends_free_bench_util import batch_call, events_ms, model_check, short_pairs, wall_ms
 
 
 def _i32_scheme(saln, q_off, d_off, pairs):
@@ -81,7 +49,6 @@ def main():
     import torch
     import sequencealigning_amd as saln
     from sequencealigning_amd import _lib, synth
-    import ends_free_model as model
 
     ef = saln.ends_free
     L = _lib.lib()
@@ -95,15 +62,8 @@ def main():
         qs = [allq[k * lq:(k + 1) * lq] for k in range(a.distinct)]
         if ld == lq:
             ds = [(synth.mutate(q, 0.05, seed=k) + q)[:ld] for k, q in enumerate(qs)]
-        else:   # the read's mutated copy inside a random window
-            pad = synth.random_bases(seed ^ 0xDB, a.distinct * ld).tobytes()
-            ds = []
-            for k, q in enumerate(qs):
-                w = bytearray(pad[k * ld:(k + 1) * ld])
-                m = synth.mutate(q, 0.05, seed=k)[:ld]
-                at = (k * 37) % (ld - len(m) + 1)
-                w[at:at + len(m)] = m
-                ds.append(bytes(w))
+        else:
+            qs, ds = short_pairs(synth, a.distinct, seed, lq, ld)
         q_seq, q_off = saln.pack_csr(qs)
         d_seq, d_off = saln.pack_csr(ds)
         idx = np.arange(a.pairs, dtype=np.uint32) % np.uint32(a.distinct)
@@ -121,19 +81,12 @@ def main():
             res = torch.zeros(a.pairs * 8, dtype=torch.int32, device="cuda")
             run_ef = lambda: plan.execute(dq, dd, res)                 # noqa: E731
             run_nw = lambda: nw_plan.execute(dq, dd, nw_res)           # noqa: E731
-            timer, how = _events_ms, "device resident, hipEvents"
+            timer, how = events_ms, "device resident, hipEvents"
         else:
             vp = lambda x: x.ctypes.data_as(C.c_void_p)                # noqa: E731
             pq, pd = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
             ctx = _lib.context(0)
-
-            def run_ef():
-                h = C.c_void_p()
-                _lib.check(L.saln_ends_free_align_batch(
-                    ctx, vp(q_seq), vp(q_off), len(q_off) - 1, vp(d_seq), vp(d_off), len(d_off) - 1,
-                    vp(pq), vp(pd), a.pairs, mode, None, 0, 1, C.byref(h)), "ends_free_align_batch")
-                L.saln_ends_free_aln_free(h)
-
+            run_ef = batch_call("saln_ends_free_align_batch", q_seq, q_off, d_seq, d_off, pq, pd, mode, None, 1)
             nw_out = np.zeros(a.pairs, dtype=_lib.RESULT_DTYPE)
             coff = np.arange(a.pairs + 1, dtype=np.uint64) * np.uint64(lq + ld)
             nw_cig = np.zeros(int(coff[-1]), np.uint32)
@@ -145,7 +98,7 @@ def main():
                     vp(pq), vp(pd), a.pairs, 0, sarg, vp(nw_out), vp(nw_cig), vp(coff)),
                     "nw_align_batch")
 
-            timer, how = _wall_ms, "host buffers in, CIGARs out, wall clock of the C call"
+            timer, how = wall_ms, "host buffers in, CIGARs out, wall clock of the C call"
         t_ef, t_nw = [], []
         for _ in range(a.alternations):
             t_ef += timer(run_ef, a.warmup, a.steps)
@@ -154,11 +107,7 @@ def main():
         k = min(a.check, a.distinct)
         got, cig = ef.ends_free_align_batch(qs[:k], ds[:k], [(j, j) for j in range(k)], mode=mode,
                                             cigar=cigar)
-        ok = True
-        for j in range(k):
-            m = model.align(qs[j], ds[j], mode, walk=cigar)
-            ok &= tuple(int(v) for v in got[j]) == m.record()
-            ok &= cig.words(j).tolist() == model.cigar_words(m.cigar)
+        ok = model_check(got, cig, qs, ds, mode, None, cigar)
         med_ef, med_nw = float(np.median(t_ef)), float(np.median(t_nw))
         out["workloads"].append({
             "name": name, "timing": how, "len_q": lq, "len_db": ld,
@@ -168,7 +117,7 @@ def main():
             "nw_i32_ms": round(med_nw, 3), "nw_i32_gcups": round(cells / med_nw / 1e6, 1),
             "nw_i32_ms_min_max": [round(min(t_nw), 3), round(max(t_nw), 3)],
             "ratio_ends_free_over_nw": round(med_nw / med_ef, 3),
-            "samples_each": len(t_ef), "model_check": {"pairs": k, "ok": bool(ok)},
+            "samples_each": len(t_ef), "model_check": {"pairs": k, "ok": ok},
         })
         nw_plan.close()
         if not cigar:

@@ -17,28 +17,12 @@ linear-memory model of tests/test_ends_free_long.py, and its CIGAR with itself
 --out (default profiles/ends_free_long_bench.json).
 """
 import argparse
-import ctypes as C
 import json
 import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-
-def _wall_ms(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return ts
+from ends_free_bench_util import ROOT, batch_call, long_pairs, model_check, wall_ms
 
 
 def main():
@@ -55,25 +39,13 @@ def main():
     assert a.steps >= 10, "at least 10 timed steps"
     import torch
     import sequencealigning_amd as saln
-    from sequencealigning_amd import _lib, synth
-    import ends_free_model as model
+    from sequencealigning_amd import synth
     from test_ends_free_long import linear_ends
 
     ef = saln.ends_free
-    L = _lib.lib()
-    ctx = _lib.context(0)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
     lq, ld = 2048, 2000
     seed = 0x5EED10F6
-    allq = synth.random_bases(seed, a.distinct * lq).tobytes()
-    pad = synth.random_bases(seed ^ 0xDB, a.distinct * ld).tobytes()
-    qs = [allq[k * lq:(k + 1) * lq] for k in range(a.distinct)]
-    ds = []
-    for k, q in enumerate(qs):   # 1,600 db rows of the query's mutated middle inside a random window
-        w = bytearray(pad[k * ld:(k + 1) * ld])
-        m = synth.mutate(q[200:1800], 0.05, seed=k)[:1600]
-        w[200:200 + len(m)] = m
-        ds.append(bytes(w))
+    qs, ds = long_pairs(synth, a.distinct, seed, lq, ld)
     halves = [h for q in qs for h in (q[:1024], q[1024:])]
     assert ef.pair_path_long(lq, ld) == (1, 2) and ef.pair_path_long(1024, ld) == (0, 1)
     q_seq, q_off = saln.pack_csr(qs)
@@ -84,29 +56,19 @@ def main():
     hd = np.ascontiguousarray(np.repeat(idx, 2))
     cells = float(lq) * ld * a.pairs
 
-    def batch(entry, seq, off, pq, pd, mode, want_cigar):
-        def run():
-            h = C.c_void_p()
-            _lib.check(getattr(L, entry)(
-                ctx, vp(seq), vp(off), len(off) - 1, vp(d_seq), vp(d_off), len(d_off) - 1, vp(pq),
-                vp(pd), len(pq), mode, None, 0, want_cigar, C.byref(h)), entry)
-            L.saln_ends_free_aln_free(h)
-        return run
-
     out = {"pairs": a.pairs, "distinct": a.distinct, "steps": a.steps, "warmup": a.warmup,
            "alternations": a.alternations, "device": torch.cuda.get_device_name(0), "workloads": []}
     for name, mode in (("local 2048x2000 score only", 1), ("semi-global 2048x2000 score only", 2)):
-        run_long = batch("saln_ends_free_long_align_batch", q_seq, q_off, idx, idx, mode, 0)
-        run_cls = batch("saln_ends_free_align_batch", h_seq, h_off, hq, hd, mode, 0)
+        run_long = batch_call("saln_ends_free_long_align_batch", q_seq, q_off, d_seq, d_off, idx, idx, mode, None, 0)
+        run_cls = batch_call("saln_ends_free_align_batch", h_seq, h_off, d_seq, d_off, hq, hd, mode, None, 0)
         t_long, t_cls = [], []
         for _ in range(a.alternations):
-            t_long += _wall_ms(run_long, a.warmup, a.steps)
-            t_cls += _wall_ms(run_cls, a.warmup, a.steps)
+            t_long += wall_ms(run_long, a.warmup, a.steps)
+            t_cls += wall_ms(run_cls, a.warmup, a.steps)
         k = min(a.check, a.distinct)
         got, _ = ef.ends_free_align_long_batch(qs[:k], ds[:k], [(j, j) for j in range(k)], mode=mode,
                                                cigar=False)
-        ok = all(tuple(int(v) for v in got[j]) == model.align(qs[j], ds[j], mode, walk=False).record()
-                 for j in range(k))
+        ok = model_check(got, None, qs, ds, mode, None, False)
         med_long, med_cls = float(np.median(t_long)), float(np.median(t_cls))
         out["workloads"].append({
             "name": name, "timing": "host buffers in, records out, wall clock of the C call",
@@ -117,7 +79,7 @@ def main():
             "ratio_long_over_class_fill": round(med_cls / med_long, 3),
             "long_ms_samples": [round(t, 3) for t in t_long],
             "class_fill_ms_samples": [round(t, 3) for t in t_cls],
-            "model_check": {"pairs": k, "ok": bool(ok)},
+            "model_check": {"pairs": k, "ok": ok},
         })
     if a.lone:
         n = a.lone
@@ -131,7 +93,7 @@ def main():
 
         ts = []
         for _ in range(a.alternations):
-            ts += _wall_ms(run_lone, a.warmup, a.steps)
+            ts += wall_ms(run_lone, a.warmup, a.steps)
         r, cigar = lone["res"], lone["cig"]
         score, q_end, db_end = linear_ends(q, d, 1)
         ok = (int(r["score"]), int(r["q_end"]), int(r["db_end"])) == (score, q_end, db_end)

@@ -21,7 +21,6 @@ one JSON line and writes it, with every sample, to --out (default
 profiles/ends_free_replay_bench.json).  --tile-rows 0: the option's default.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -29,19 +28,7 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _wall_ms(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return ts
+from ends_free_bench_util import ROOT, batch_call, wall_ms
 
 
 def _stats(ts):
@@ -64,12 +51,9 @@ def main():
     from sequencealigning_amd import _lib, synth
 
     ef = saln.ends_free
-    L = _lib.lib()
-    ctx = _lib.context(0)
     if a.tile_rows:
         _lib.set_option("ends_free.tile_rows", a.tile_rows)
     R = _lib.get_option("ends_free.tile_rows")[0]
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
     seed = 0x5EED7113
 
     def square(n, count, s):
@@ -117,24 +101,16 @@ def main():
         d_seq, d_off = saln.pack_csr(ds)
         idx = np.arange(n, dtype=np.uint32)
 
-        def batch(entry):
-            def run():
-                h = C.c_void_p()
-                _lib.check(getattr(L, entry)(ctx, vp(q_seq), vp(q_off), n, vp(d_seq), vp(d_off), n, vp(idx),
-                                             vp(idx), n, mode, None, 0, 1, C.byref(h)), entry)
-                L.saln_ends_free_aln_free(h)
-            return run
-
-        run_replay = batch("saln_ends_free_replay_align_batch")
-        run_long = batch("saln_ends_free_long_align_batch")
+        run_replay, run_long = (batch_call(entry, q_seq, q_off, d_seq, d_off, idx, idx, mode, None, 1)
+                                for entry in ("saln_ends_free_replay_align_batch", "saln_ends_free_long_align_batch"))
         t0 = time.perf_counter()
         run_long()
         slow = time.perf_counter() - t0 > 1.0
         warmup, steps = (1, 2) if slow else (a.warmup, a.steps)
         t_replay, t_long = [], []
         for _ in range(a.alternations):
-            t_replay += _wall_ms(run_replay, warmup, steps)
-            t_long += _wall_ms(run_long, warmup, steps)
+            t_replay += wall_ms(run_replay, warmup, steps)
+            t_long += wall_ms(run_long, warmup, steps)
         k = min(a.check, n)
         pairs = [(j, j) for j in range(k)]
         got, gcig = ef.ends_free_align_long_batch(qs[:k], ds[:k], pairs, mode=mode, replay=True)

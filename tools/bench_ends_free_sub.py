@@ -18,7 +18,7 @@ The class fills (150 x 150: 16 x 10; 250 x 250: 16 x 16; 500 x 500: 64 x 8;
 hipEvents; the chunked fill (2,048 x 2,000) as the wall clock of the C call,
 host buffers in, records out.  The three are measured in alternation in the
 same process.  GCUPS = len_q * len_db * pairs / time.  A sample of the protein
-pairs is compared with tests/ends_free_sub_model.py.  Prints one JSON line and
+pairs is compared with tests/ends_free_model.py.  Prints one JSON line and
 writes it, with every sample, to --out (default
 profiles/ends_free_sub_bench.json).
 """
@@ -26,44 +26,13 @@ import argparse
 import json
 import os
 import random
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from ends_free_bench_util import ROOT, events_ms, wall_ms
 
 SCALAR = (5, -4, -8, -6)
 PROTEIN = b"ARNDCQEGHILKMFPSTWYVBZXU"
-
-
-def _events_ms(fn, warmup, steps):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return ts
-
-
-def _wall_ms(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return ts
 
 
 def _protein_pairs(distinct, lq, ld, seed):
@@ -95,7 +64,7 @@ def main():
     import torch
     import sequencealigning_amd as saln
     from sequencealigning_amd import synth
-    import ends_free_sub_model as model
+    import ends_free_model as model
 
     ef = saln.ends_free
     table4 = [[SCALAR[0] if x == y else SCALAR[1] for y in range(4)] for x in range(4)]
@@ -128,7 +97,7 @@ def main():
                     last[name] = ef.ends_free_align_long_batch(seqs[0], seqs[1], pairs, mode=mode, scoring=sc,
                                                                cigar=False)[0]
                 runs[name] = run
-            timer, how = _wall_ms, "host buffers in, records out, wall clock of ends_free_align_long_batch"
+            timer, how = wall_ms, "host buffers in, records out, wall clock of ends_free_align_long_batch"
         else:
             keep = []
             for name, seqs, sc in (("scalar", (qs, ds), SCALAR), ("matrix", (qs, ds), sm4),
@@ -142,7 +111,7 @@ def main():
                 keep.append(plan)
                 last[name] = res
                 runs[name] = lambda plan=plan, dq=dq, dd=dd, res=res: plan.execute(dq, dd, res)
-            timer, how = _events_ms, "EndsFreePlan, device resident, hipEvents"
+            timer, how = events_ms, "EndsFreePlan, device resident, hipEvents"
         ts = {name: [] for name in runs}
         for _ in range(a.alternations):
             for name, run in runs.items():

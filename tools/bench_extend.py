@@ -10,51 +10,18 @@ first byte on, so that the extension runs the pair's length):
   1,000 x 1,000  25,000 pairs, the same
   2,048 x 2,000  4,096 pairs, the chunked fill (saln_ends_free_long_align_batch,
                  host buffers in, records out, wall clock of the C call)
-A sample of every workload and mode is checked against the models
-(tests/extend_model.py, tests/ends_free_sub_model.py).  Prints one JSON line.
+A sample of every workload and mode is checked against the model
+(tests/ends_free_model.py).  Prints one JSON line.
 """
 import argparse
-import ctypes as C
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from ends_free_bench_util import batch_call, events_ms, model_check, wall_ms
 
 LOCAL, EXTEND = 1, 8
 SCORING = (5, -4, -8, -6)
-
-
-def _events_ms(fn, warmup, steps):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return ts
-
-
-def _wall_ms(fn, warmup, steps):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return ts
 
 
 def main():
@@ -69,14 +36,8 @@ def main():
     import torch
     import sequencealigning_amd as saln
     from sequencealigning_amd import _lib, synth
-    import ends_free_sub_model as sub_model
-    import extend_model
 
     ef = saln.ends_free
-    L = _lib.lib()
-    ctx = _lib.context(0)
-    msc = extend_model.scalar_scoring(*SCORING)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)   # noqa: E731
     out = {"steps": a.steps, "warmup": a.warmup, "alternations": a.alternations, "scoring": list(SCORING),
            "device": torch.cuda.get_device_name(0), "workloads": []}
     for name, lq, ld, n_pairs, distinct, chunked in (("150x150 score only", 150, 150, 100_000, 2_000, False),
@@ -102,37 +63,24 @@ def main():
                 res = torch.zeros(n_pairs * 8, dtype=torch.int32, device="cuda")
                 runs[mode] = lambda plan=plan, res=res: plan.execute(dq, dd, res)
                 plans.append(plan)
-            timer, how = _events_ms, "EndsFreePlan, device resident, hipEvents"
+            timer, how = events_ms, "EndsFreePlan, device resident, hipEvents"
         else:
-            sarg = _lib.scoring_arg(SCORING)
-
-            def batch(mode):
-                def run():
-                    h = C.c_void_p()
-                    _lib.check(L.saln_ends_free_long_align_batch(
-                        ctx, vp(q_seq), vp(q_off), len(q_off) - 1, vp(d_seq), vp(d_off), len(d_off) - 1,
-                        vp(idx), vp(idx), n_pairs, mode, sarg, 0, 0, C.byref(h)), "ends_free_long_align_batch")
-                    L.saln_ends_free_aln_free(h)
-                return run
-
-            runs = {mode: batch(mode) for mode in (LOCAL, EXTEND)}
-            timer, how = _wall_ms, "host buffers in, records out, wall clock of the C call"
+            runs = {mode: batch_call("saln_ends_free_long_align_batch", q_seq, q_off, d_seq, d_off, idx, idx,
+                                     mode, _lib.scoring_arg(SCORING), 0) for mode in (LOCAL, EXTEND)}
+            timer, how = wall_ms, "host buffers in, records out, wall clock of the C call"
         ts = {LOCAL: [], EXTEND: []}
         for _ in range(a.alternations):
             for mode in (LOCAL, EXTEND):
                 ts[mode] += timer(runs[mode], a.warmup, a.steps)
         for plan in plans:
             plan.close()
-        # a sample against the models
+        # a sample against the model
         k = min(a.check, distinct)
         ok = True
         for mode in (LOCAL, EXTEND):
             got, _ = ef.ends_free_align_long_batch(qs[:k], ds[:k], [(j, j) for j in range(k)], mode=mode,
                                                    scoring=SCORING, cigar=False)
-            for j in range(k):
-                m = (extend_model.align(qs[j], ds[j], msc, walk=False) if mode == EXTEND
-                     else sub_model.align(qs[j], ds[j], sub_model.LOCAL, msc, walk=False))
-                ok &= tuple(int(v) for v in got[j]) == m.record()
+            ok &= model_check(got, None, qs, ds, mode, SCORING, False)
         med = {mode: float(np.median(t)) for mode, t in ts.items()}
         out["workloads"].append({
             "name": name, "timing": how, "len_q": lq, "len_db": ld, "pairs": n_pairs,
@@ -141,7 +89,7 @@ def main():
             "extend_ms_min_max": [round(min(ts[EXTEND]), 3), round(max(ts[EXTEND]), 3)],
             "local_gcups": round(cells / med[LOCAL] / 1e6, 1), "extend_gcups": round(cells / med[EXTEND] / 1e6, 1),
             "extend_over_local_time": round(med[EXTEND] / med[LOCAL], 4),
-            "samples_each": len(ts[LOCAL]), "model_check": {"pairs": k, "ok": bool(ok)},
+            "samples_each": len(ts[LOCAL]), "model_check": {"pairs": k, "ok": ok},
         })
     print(json.dumps(out))
     if not all(w["model_check"]["ok"] for w in out["workloads"]):
