@@ -1,6 +1,6 @@
 // What every host file of the engine needs and nothing engine-specific: the
-// context, error reporting, scoped device memory, pair resolution, the host
-// thread fan-out and the upload / host-buffer helpers (host_common.cpp).
+// context, error reporting, scoped device memory, pair resolution
+// (pair_index.hpp), the host thread fan-out and the upload / host-buffer helpers (host_common.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <utility>
 
+#include "pair_index.hpp"
 #include "saln_options.hpp"
 #include "saln.h"
 
@@ -58,8 +59,6 @@ inline hipStream_t resolve_stream(void *stream, const saln_context *ctx) {
 }
 
 namespace saln {
-
-void set_error(const std::string &msg);
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
@@ -135,39 +134,6 @@ struct DevBuf {
     template <typename T>
     T *as() const { return static_cast<T *>(p); }
 };
-
-// Pair k of a batch: the caller's index lists, or without them the q-major
-// grid over n_q x n_db (db-outer, query-inner, as the reference's loop).
-struct PairIndex {
-    const uint32_t *pair_q, *pair_db;
-    uint64_t n_q, n_db;
-    // plans: both lists or neither, and without them n_pairs is the whole grid
-    bool complete(uint64_t n_pairs) const {
-        if (!pair_q != !pair_db) return false;
-        if (pair_q || n_pairs == n_q * n_db) return true;
-        set_error("all-vs-all needs n_pairs == n_q * n_db");
-        return false;
-    }
-    // false ("pair index out of range") for an index outside the sets
-    bool at(uint64_t k, uint64_t *qi, uint64_t *di) const {
-        *qi = pair_q ? pair_q[k] : n_q ? k % n_q : 0;
-        *di = pair_db ? pair_db[k] : n_q ? k / n_q : 0;
-        if (*qi < n_q && *di < n_db) return true;
-        set_error("pair index out of range");
-        return false;
-    }
-};
-
-// The lengths of query qi and db record di from the offset tables; false
-// ("sequence too long") when one exceeds the engine's limit.
-inline bool pair_lengths(const uint64_t *q_off, const uint64_t *db_off, uint64_t qi, uint64_t di,
-                         uint64_t limit, uint64_t *lq, uint64_t *ld) {
-    *lq = q_off[qi + 1] - q_off[qi];
-    *ld = db_off[di + 1] - db_off[di];
-    if (*lq <= limit && *ld <= limit) return true;
-    set_error("sequence too long");
-    return false;
-}
 
 // Work items [0, n) on up to `threads` host threads (the caller included, at
 // most 16 and the machine's), handed out in blocks of `grain`.

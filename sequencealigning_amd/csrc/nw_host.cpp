@@ -5,6 +5,12 @@
 // runs in the HIP kernels of nw_kernels.hip; the host only plans batches,
 // moves buffers and, for the reference's text output, walks the parent codes
 // the GPU produced (the reference's exhaustive DFS, :281-329).
+//
+// What a plan decides (variants, plan order, every offset, the stripe work
+// list, the speculative tables) is decided in nw_plan_layout.cpp, without
+// HIP; this file holds the plan's device state: plan_create allocates and
+// uploads what the layout says, PlanOwned owns every block and event, and
+// saln_nw_execute launches over them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,7 +18,6 @@
 #include <array>
 #include <cstring>
 #include <map>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <unordered_set>
@@ -20,53 +25,55 @@
 
 #include "nw_host.hpp"
 
-namespace saln {
-
-Scoring scoring_or_default(const saln_nw_scoring *s) {
-    if (!s) return Scoring{5, -4, -8, -6};  // SCHEME, needleman_wunsch_affine.rs:15-20
-    return Scoring{s->match, s->mismatch, s->gap_open, s->gap_extend};
-}
-
-// The i32 fills carry V'' = 4V + 2a + p plus the position offsets alpha*r +
-// beta*c (nw_common.hpp).  |V| is at most the sentinel plus one step's
-// largest change per row and column of the path; a pair passes while that
-// bound, scaled and offset, stays inside int32 (the reference's own i32
-// arithmetic is exact far beyond it: the pairs rejected here are ~10^8 long
-// or carry penalties of ~10^4).
-bool scores_fit_i32(const Scoring &s, uint64_t lq, uint64_t ld) {
-    auto a = [](int64_t v) { return v < 0 ? -v : v; };
-    const int64_t step = std::max({a(s.match), a(s.mismatch), a(s.gap_open) + a(s.gap_extend)});
-    const long double v = 32768.0L + (long double)(lq + ld) * (long double)step;
-    const long double off = 4.0L * (a(s.match) + 2 * a(s.gap_extend)) * (long double)ld +
-                            4.0L * a(s.gap_extend) * (long double)lq;
-    return 4.0L * v + 3.0L + off < 2147483647.0L;
-}
-
-}  // namespace saln
-
 using namespace saln;
 
 // a plan's table-fill bail words per mask workspace: one per fill variant
 constexpr size_t kBailBytes = kNumVariants * sizeof(uint32_t);
 
-struct saln_nw_plan {
+// Every device block and event of a plan: what alloc() and event() hand out
+// is recorded here and released here, all of it, however far creation got.
+// The plan's typed pointers are views.  Blocks go back to the context cache,
+// so nothing may still use them: saln_nw_plan_destroy syncs the device first.
+struct PlanOwned {
     saln_context *ctx = nullptr;
+    std::vector<void *> blocks;
+    std::vector<hipEvent_t> events;
+    PlanOwned() = default;
+    PlanOwned(const PlanOwned &) = delete;
+    PlanOwned &operator=(const PlanOwned &) = delete;
+    template <typename T>
+    hipError_t alloc(T **p, size_t bytes) {
+        void *b = nullptr;
+        const hipError_t e = dev_alloc(ctx, &b, bytes);
+        if (e != hipSuccess) return e;
+        blocks.push_back(b);
+        *p = static_cast<T *>(b);
+        return hipSuccess;
+    }
+    hipError_t event(hipEvent_t *ev, unsigned flags = hipEventDefault) {
+        const hipError_t e = hipEventCreateWithFlags(ev, flags);
+        if (e == hipSuccess) events.push_back(*ev);
+        return e;
+    }
+    ~PlanOwned() {
+        for (void *b : blocks) dev_free(ctx, b);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+};
+
+// The layout (nw_plan_layout.hpp: pairs in plan order, offsets, stripe layout,
+// work list, speculative tables) and the device state built from it.
+struct saln_nw_plan : NwPlanLayout {
+    saln_context *ctx = nullptr;
+    PlanOwned own;
     Options opts{};  // the context's effective options at creation
     Scoring sc{};
     uint64_t n_pairs = 0;
-    std::vector<NwPairDesc> h_pairs;  // plan order
-    std::vector<uint32_t> plan_index;  // results index -> plan order
     NwPairDesc *d_pairs = nullptr;
-    uint32_t var_first[kNumVariants] = {}, var_count[kNumVariants] = {};
-    uint32_t var_maxld[kNumVariants] = {};  // longest db of each variant's pairs
-    uint32_t n_fill = 0;  // plan order: [0, n_fill) filled pairs, then empty-side pairs
     uint8_t *d_mask = nullptr;
     uint8_t *d_mask2 = nullptr;  // second workspace for the async (2-deep) pipeline
     int32_t *d_endh2 = nullptr;
     bool async_tb = false;
-    bool stripe_pk = false;  // column stripes use the packed fill and layout
-    int stripe_rows = 0;     // else: row fill with this many columns per lane (0 = skewed fill)
-    uint32_t stripe_sub = kStripeSubMax;  // boundary columns per 256-column chunk
     int stripe_layout() const { return stripe_pk ? 1 : stripe_rows ? 2 : 0; }
     // launch_fill's code format for variant v and whether its launch has a bail word
     int fill_codes(int v) const {
@@ -74,18 +81,13 @@ struct saln_nw_plan {
     }
     bool has_bail() const { return d_bail[async_tb ? buf : 0] != nullptr; }
     bool full_codes = false;  // walk codes (default) or every parent set (decided at creation)
-    bool nib[kNumVariants] = {};  // variant stores 4-bit walk codes (Geom::LBn segments)
     bool score_only = false;  // no parent codes / traceback (saln_nw_plan_set_score_only)
     int buf = 0;                           // workspace of the next execute (async mode)
     hipStream_t tb_stream = nullptr;       // traceback stream of async executes (NULL: ctx's)
     bool tb_pending[2] = {false, false};
     int last_buf = 0;
-    uint64_t mask_bytes = 0;
     int2 *d_scratch = nullptr;
-    // column-stripe pairs (kStripeVariant): work items (plan index, chunk),
-    // per-pair first work item (plan order, n_pairs+1), progress counters
-    uint2 *d_work = nullptr;
-    std::vector<uint32_t> work_first;
+    uint2 *d_work = nullptr;  // the layout's stripe work list
     // d_err[0]: device error flags since the last saln_nw_plan_status (bit 0
     // a dependency wait timed out, bit 1 an unlinked speculative walk under
     // SALN_SPEC_STRICT); d_err[1]: the wait limit the fills read
@@ -93,27 +95,20 @@ struct saln_nw_plan {
     uint32_t fill_epoch = 0;  // stripe fills launched (the XCD slots' epochs)
     uint32_t wait_limit = kWaitLimitDefault;
     bool unchecked[2] = {false, false};  // executes on workspace b since the last status
-    uint64_t n_prog = 0;
     uint32_t *d_ops = nullptr;  // traceback op-stream scratch of workspace 0
     uint32_t *d_ops2 = nullptr;  // ... of workspace 1 (async: its walks may overlap workspace 0's)
-    uint64_t ops_words = 0;
     // per workspace: the table fills' bail word (zeroed once; a table launch
     // whose waves left pairs to its fallback launch stores its epoch there)
     uint32_t *d_bail[2] = {nullptr, nullptr};
     uint32_t epoch = 0;  // table launches of this plan (the bail word's values)
-    // speculative stripe walks (a few long column-stripe pairs): block map,
-    // pairs, stripe records, run words, per-pair done flags (plan order)
+    // speculative stripe walks: the layout's block map and pairs on the
+    // device, stripe records, run words, per-pair done flags (plan order)
     uint32_t spec_pairs = 0, spec_blocks = 0;
-    int spec_passes = 0;
-    bool spec_strict = false;  // SALN_SPEC_STRICT=1: a pair left to the cooperative walker is an error
     uint2 *d_spec_blocks = nullptr;
     SpecPair *d_spec_pairs = nullptr;
     SpecStripe *d_spec_stripes = nullptr;
     uint32_t *d_spec_ops = nullptr, *d_spec_done = nullptr;
-    uint64_t scratch_elems = 0;
     int32_t *d_endh = nullptr;
-    std::vector<uint64_t> cigar_off;  // results order, n_pairs + 1
-    uint64_t cells = 0;
     bool timing = false;
     // hipEvents around the fill and traceback launches of each execute;
     // resolved lazily (no host sync inside execute).
@@ -127,6 +122,8 @@ struct saln_nw_plan {
     // done" (two events)
     std::vector<hipEvent_t> sync_ev;
 };
+// the layout's two-word items are copied to the device as uint2
+static_assert(sizeof(Word2) == sizeof(uint2), "Word2 is read as uint2");
 
 extern "C" {
 
@@ -200,17 +197,7 @@ int saln_nw_plan_destroy(saln_nw_plan *p) {
     if (!p) return SALN_OK;
     (void)hipSetDevice(p->ctx->device);
     (void)hipDeviceSynchronize();  // the blocks go back to the context cache
-    for (void *b : {(void *)p->d_pairs, (void *)p->d_mask, (void *)p->d_mask2, (void *)p->d_endh2,
-                    (void *)p->d_scratch, (void *)p->d_work, (void *)p->d_prog, (void *)p->d_err,
-                    (void *)p->d_ops, (void *)p->d_ops2, (void *)p->d_bail[0], (void *)p->d_bail[1],
-                    (void *)p->d_endh, (void *)p->d_spec_blocks,
-                    (void *)p->d_spec_pairs, (void *)p->d_spec_stripes, (void *)p->d_spec_ops,
-                    (void *)p->d_spec_done})
-        dev_free(p->ctx, b);
-    for (auto &e : p->sync_ev) (void)hipEventDestroy(e);
-    for (auto &t : p->ev_pool)
-        for (auto &e : t) (void)hipEventDestroy(e);
-    delete p;
+    delete p;                      // PlanOwned releases every block and event
     return SALN_OK;
 }
 
@@ -293,343 +280,88 @@ int saln_nw_plan_walk_codes(saln_nw_plan *p, uint64_t pair, uint8_t *out) {
 
 }  // extern "C"
 
-// Plan creation.  full_codes: the fills store every parent set (host DFS,
-// dense mask) instead of walk codes; it fixes the mask layout (4-bit walk
-// codes for the short-query packed variants, bytes otherwise).
+// Plan creation: the layout (nw_plan_layout.cpp decides everything), then
+// the device blocks it asks for, then the uploads.  A failure on the way
+// destroys the plan, which releases whatever it owns by then.
 int saln::plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
                       const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
                       const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
                       const saln_nw_scoring *scoring, bool full_codes, saln_nw_plan **out) {
     if (!ctx || !q_off || !db_off || !out) return SALN_E_INVALID;
     *out = nullptr;
-    if (mode != SALN_MODE_GLOBAL) {
-        set_error("not implemented");  // needleman_wunsch_affine.rs:433-434
-        return SALN_NOT_IMPLEMENTED;
-    }
-    const PairIndex pairs{pair_q, pair_db, n_q, n_db};
-    if (!pairs.complete(n_pairs) || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     HIP_TRY(hipSetDevice(ctx->device));
     const Options opts = ctx->opts.effective();
     StageClock clk(opts);
-    auto *p = new saln_nw_plan;
-    p->ctx = ctx;
-    p->opts = opts;
-    p->sc = scoring_or_default(scoring);
-    p->full_codes = full_codes;
-    // 4-bit walk codes for the short-query packed variants: 8 x 19 groups for
-    // queries of <= 152 columns, 16 x 10 up to 160; full-code plans keep byte
-    // codes and the 16 x 10 groups
-    const bool nib_on = !full_codes;
-    const bool narrow = nib_on;
-    for (int v = 0; v < kNumVariants; ++v) p->nib[v] = nib_on && variant_nib(v);
-    p->n_pairs = n_pairs;
-    p->cigar_off.resize(n_pairs + 1);
-    std::vector<NwPairDesc> descs(n_pairs);
-    uint64_t cig = 0;
-    // the range check and the variant depend on the shape only: batches of
-    // alike pairs (the usual case) decide once per shape, not per pair
-    uint64_t memo_lq = ~0ull, memo_ld = ~0ull;
-    bool memo_fit = false;
-    int memo_var = 0;
-    for (uint64_t k = 0; k < n_pairs; ++k) {
-        uint64_t qi, di, lq, ld;
-        if (!pairs.at(k, &qi, &di) ||
-            !pair_lengths(q_off, db_off, qi, di, 0x7FFFFFFFull, &lq, &ld)) {
-            delete p;
-            return SALN_E_INVALID;
-        }
-        NwPairDesc &d = descs[k];
-        std::memset(&d, 0, sizeof(d));
-        d.q_off = q_off[qi];
-        d.db_off = db_off[di];
-        if (lq != memo_lq || ld != memo_ld) {
-            memo_lq = lq;
-            memo_ld = ld;
-            memo_fit = scores_fit_i32(p->sc, lq, ld);
-            memo_var = memo_fit ? choose_variant((uint32_t)lq, (uint32_t)ld, p->sc, narrow) : 0;
-        }
-        if (!memo_fit) {
-            delete p;
-            set_error("pair too long for these penalties: its scores could leave the engine's "
-                      "int32 range");
-            return SALN_E_INVALID;
-        }
-        d.len_q = (uint32_t)lq;
-        d.len_db = (uint32_t)ld;
-        d.pair_id = (uint32_t)k;
-        d.variant = (uint32_t)memo_var;
-        d.cigar_off = cig;
-        p->cigar_off[k] = cig;
-        cig += lq + ld;
-        p->cells += lq * ld;
-    }
-    p->cigar_off[n_pairs] = cig;
-    clk.mark("plan: descs");
-    demote_wide_pairs(descs.data(), descs.size(), opts);
-    // plan order: fill pairs grouped by variant, then by query chunk count,
-    // longest db first (balances the groups of a block and keeps the pairs of
-    // a mask pack alike); pairs with an empty side last (traceback only).
-    // (variant, ~chunks, ~len_db) packed in one word, ties by results index;
-    // a batch of alike pairs is usually in order already
-    std::vector<uint64_t> skey(n_pairs);
-    for (uint64_t k = 0; k < n_pairs; ++k) {
-        const NwPairDesc &d = descs[k];
-        const bool empty = d.len_q == 0 || d.len_db == 0;
-        const uint64_t nch = empty ? 0 : variant_geom((int)d.variant).n_chunks(d.len_q);
-        skey[k] = (uint64_t)(empty ? (uint32_t)kNumVariants : d.variant) << 56 |
-                  ((~nch) & 0xFFFFFFull) << 32 | (uint32_t)~d.len_db;
-    }
-    std::vector<uint32_t> order;
-    const bool in_order = std::is_sorted(skey.begin(), skey.end());
-    if (in_order) {
-        p->h_pairs = std::move(descs);  // plan order = results order: no copy
-    } else {
-        order.resize(n_pairs);
-        std::iota(order.begin(), order.end(), 0u);
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-            return skey[a] != skey[b] ? skey[a] < skey[b] : a < b;
-        });
-        p->h_pairs.resize(n_pairs);
-    }
-    clk.mark("plan: sort");
-    uint64_t soff = 0, ooff = 0;
-    for (uint64_t r = 0; r < n_pairs; ++r) {
-        NwPairDesc d = in_order ? p->h_pairs[r] : descs[order[r]];
-        const bool empty = d.len_q == 0 || d.len_db == 0;
-        if (!empty) {
-            const Geom g = variant_geom((int)d.variant);
-            d.ops_off = ooff;
-            ooff += (d.len_q + d.len_db + 9) / 10 + 1;  // 3-bit ops, ten per word
-            if (g.n_chunks(d.len_q) > 1 || d.variant == kStripeVariant) {
-                soff = (soff + 3) & ~3ull;  // 32-byte aligned columns (nw_fill_rows_kernel)
-                d.scratch_off = soff;
-                // stripes run concurrently: one boundary column per chunk boundary
-                soff += (uint64_t)(d.variant == kStripeVariant ? kStripeSubMax * g.n_chunks(d.len_q)
-                                                                : 1) *
-                        scratch_col(d.len_db);
-            }
-            if (p->var_count[d.variant] == 0) p->var_first[d.variant] = (uint32_t)r;
-            p->var_count[d.variant]++;
-            p->var_maxld[d.variant] = std::max(p->var_maxld[d.variant], d.len_db);
-            p->n_fill++;
-        }
-        p->h_pairs[r] = d;
-    }
-    {
-        uint64_t waves = 0, cols = 0, waves_k1 = 0;  // 256-column chunks, columns, 64-column stripes
-        bool free_all = true;  // the packed stripes carry no alive flag (nw_common.hpp)
-        for (uint32_t r = 0; r < p->var_count[kStripeVariant]; ++r) {
-            const NwPairDesc &d = p->h_pairs[p->var_first[kStripeVariant] + r];
-            waves += variant_geom(kStripeVariant).n_chunks(d.len_q);
-            waves_k1 += (d.len_q + 63) / 64;
-            cols += d.len_q;
-            free_all = free_all && sentinel_free(p->sc, d.len_q, d.len_db);
-        }
-        // packed stripes (int16x2, throughput) for batches of wide pairs; the
-        // row fill (i32, latency) otherwise: 400 x 2 kbp^2 828 vs 678 GCUPS,
-        // 400 x 5 kbp^2 953 vs 1,204 (one box, round 2)
-        const bool wide = p->var_count[kStripeVariant] &&
-                          cols / p->var_count[kStripeVariant] >= 3000;
-        p->stripe_pk = waves > 0 && free_all && stripe_packed(p->sc, waves, wide, opts);
-        p->stripe_rows = p->stripe_pk ? 0 : stripe_rows_k(waves_k1, opts);
-        // boundary columns per 256-column chunk: the row fill's 4 / K stripes,
-        // else one; the scratch offsets above reserved kStripeSubMax
-        p->stripe_sub = p->stripe_rows ? 4u / (uint32_t)p->stripe_rows : 1u;
-        if (p->stripe_sub != kStripeSubMax) {
-            uint64_t so = 0;
-            for (uint64_t r = 0; r < p->n_fill; ++r) {
-                NwPairDesc &d = p->h_pairs[r];
-                const Geom g = variant_geom((int)d.variant);
-                if (g.n_chunks(d.len_q) > 1 || d.variant == kStripeVariant) {
-                    so = (so + 3) & ~3ull;
-                    d.scratch_off = so;
-                    so += (uint64_t)(d.variant == kStripeVariant ? p->stripe_sub * g.n_chunks(d.len_q) : 1) *
-                          scratch_col(d.len_db);
-                }
-            }
-            soff = so;
-        }
-    }
-    // Mask packs: up to 64 consecutive pairs of a variant (one traceback
-    // wave) with interleaved segments (nw_common.hpp Geom), unless padding
-    // them to the pack's longest db / widest query would cost over 25 % more
-    // than storing them apart.
-    uint64_t moff = 0;
-    for (int v = 0; v < kNumVariants; ++v) {
-        const Geom g = variant_geom(v);
-        const uint64_t lb = p->nib[v] ? g.LBn() : g.LB();
-        for (uint32_t a = p->var_first[v], e = a + p->var_count[v]; a < e; a += 64) {
-            const uint32_t np = std::min<uint32_t>(64, e - a);
-            uint64_t rows = 0, nbm = 0, own = 0;
-            for (uint32_t s = 0; s < np; ++s) {
-                const NwPairDesc &d = p->h_pairs[a + s];
-                rows = std::max<uint64_t>(rows, d.len_db);
-                nbm = std::max<uint64_t>(nbm, g.n_blocks(d.len_q));
-                own += (uint64_t)d.len_db * g.n_blocks(d.len_q) * lb;
-            }
-            const uint64_t packed = rows * nbm * np * lb;
-            if (v == kStripeVariant) {
-                // one region per 256-column chunk: the row fill's unskewed
-                // 256-column tiles (bs = 4), or the packed stripes' skewed
-                // lines (bs = 0: every fill step writes one whole line)
-                const bool pk = p->stripe_pk;
-                for (uint32_t s = 0; s < np; ++s) {
-                    NwPairDesc &d = p->h_pairs[a + s];
-                    d.mask_off = moff;
-                    d.mask_rs = g.W();
-                    d.mask_bs = pk ? 0u : (uint32_t)lb;
-                    d.mask_cs = ((uint64_t)d.len_db + (pk ? 2 * g.G : g.G) - 1) * g.W();
-                    moff += g.n_chunks(d.len_q) * d.mask_cs;
-                }
-            } else if (4 * packed <= 5 * own + 4096) {
-                for (uint32_t s = 0; s < np; ++s) {
-                    NwPairDesc &d = p->h_pairs[a + s];
-                    d.mask_off = moff + s * lb;
-                    d.mask_bs = (uint32_t)(np * lb);
-                    d.mask_rs = nbm * np * lb;
-                    d.mask_cs = (uint64_t)g.G * d.mask_bs;
-                }
-                moff += (packed + 255) & ~255ull;
-            } else {
-                for (uint32_t s = 0; s < np; ++s) {
-                    NwPairDesc &d = p->h_pairs[a + s];
-                    d.mask_off = moff;
-                    d.mask_bs = (uint32_t)lb;
-                    d.mask_rs = g.n_blocks(d.len_q) * lb;
-                    d.mask_cs = (uint64_t)g.G * lb;
-                    moff += ((uint64_t)d.len_db * d.mask_rs + 255) & ~255ull;
-                }
-            }
-        }
-    }
-    {
-        p->sync_ev.resize(3);
-        for (auto &e : p->sync_ev) {
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                e = nullptr;
-                set_error("hipEventCreate");
-                saln_nw_plan_destroy(p);
-                return SALN_E_HIP;
-            }
-        }
-    }
-    clk.mark("plan: layout");
-    p->plan_index.resize(n_pairs);
-    for (uint64_t r = 0; r < n_pairs; ++r) p->plan_index[p->h_pairs[r].pair_id] = (uint32_t)r;
-    p->mask_bytes = moff;
-    p->scratch_elems = soff;
-    auto fail = [&](hipError_t e, const char *what) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        saln_nw_plan_destroy(p);
-        return SALN_E_HIP;
+    const Scoring sc = scoring_or_default(scoring);
+    NwPlanLayout lay;
+    const int rc = nw_plan_layout(q_off, db_off, PairIndex{pair_q, pair_db, n_q, n_db}, n_pairs,
+                                  mode, sc, opts, full_codes, &lay);
+    if (rc != SALN_OK) return rc;
+    struct Destroy {
+        void operator()(saln_nw_plan *p) const { saln_nw_plan_destroy(p); }
     };
-    hipError_t e;
+    std::unique_ptr<saln_nw_plan, Destroy> p(new saln_nw_plan);
+    static_cast<NwPlanLayout &>(*p) = std::move(lay);
+    p->ctx = p->own.ctx = ctx;
+    p->opts = opts;
+    p->sc = sc;
+    p->full_codes = full_codes;
+    p->n_pairs = n_pairs;
+    p->sync_ev.resize(3);
+    for (auto &e : p->sync_ev) HIP_TRY(p->own.event(&e, hipEventDisableTiming));
+    clk.mark("plan: layout");
     if (n_pairs) {
-        if ((e = dev_alloc(p->ctx, (void **)&p->d_pairs, n_pairs * sizeof(NwPairDesc))) != hipSuccess)
-            return fail(e, "hipMalloc(pairs)");
+        const size_t nb = n_pairs * sizeof(NwPairDesc);
+        HIP_TRY(p->own.alloc(&p->d_pairs, nb));
         clk.mark("plan: pairs alloc");
         // through the context's pinned staging: a pageable copy of a freshly
         // built array pins its pages first (measured 12-17 ms for the 2.7-5.2
         // MB of a render chunk's descriptors, against ~1 ms of memcpy here)
         {
-            std::lock_guard<std::mutex> lk(p->ctx->staging_mu);
+            std::lock_guard<std::mutex> lk(ctx->staging_mu);
             void *st = nullptr;
-            const size_t nb = n_pairs * sizeof(NwPairDesc);
-            if ((e = pinned_staging(p->ctx, nb, &st)) != hipSuccess) return fail(e, "pinned staging");
+            HIP_TRY(pinned_staging(ctx, nb, &st));
             std::memcpy(st, p->h_pairs.data(), nb);
-            if ((e = hipMemcpy(p->d_pairs, st, nb, hipMemcpyHostToDevice)) != hipSuccess)
-                return fail(e, "hipMemcpy(pairs)");
+            HIP_TRY(hipMemcpy(p->d_pairs, st, nb, hipMemcpyHostToDevice));
         }
-        if ((e = dev_alloc(p->ctx, (void **)&p->d_endh, n_pairs * sizeof(int32_t))) != hipSuccess)
-            return fail(e, "hipMalloc(end)");
+        HIP_TRY(p->own.alloc(&p->d_endh, n_pairs * sizeof(int32_t)));
     }
     clk.mark("plan: pairs h2d");
     // +64 B: the traceback walker reads whole 5-dword segments
-    if (moff && (e = dev_alloc(p->ctx, (void **)&p->d_mask, moff + 64)) != hipSuccess)
-        return fail(e, "hipMalloc(mask workspace)");
-    {
-        // stripe work list (pair-major, chunk-ascending: a stripe's predecessor
-        // always has a lower workgroup id) and progress counters
-        std::vector<uint2> work;
-        p->work_first.assign(n_pairs + 1, 0);
-        for (uint64_t r = 0; r < n_pairs; ++r) {
-            NwPairDesc &d = p->h_pairs[r];
-            p->work_first[r] = (uint32_t)work.size();
-            if (d.variant != (uint32_t)kStripeVariant || !d.len_q || !d.len_db) continue;
-            const uint32_t nch = variant_geom(kStripeVariant).n_chunks(d.len_q);
-            d.reserved = (uint32_t)p->n_prog;
-            p->n_prog += nch;
-            for (uint32_t ch = 0; ch < nch; ++ch) work.push_back(make_uint2((uint32_t)r, ch));
-        }
-        p->work_first[n_pairs] = (uint32_t)work.size();
-        if (!work.empty()) {
-            if ((e = dev_alloc(p->ctx, (void **)&p->d_work, work.size() * sizeof(uint2))) != hipSuccess ||
-                (e = hipMemcpy(p->d_work, work.data(), work.size() * sizeof(uint2),
-                               hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_prog, p->n_prog * sizeof(uint32_t))) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_err, kErrWords * sizeof(uint32_t))) != hipSuccess ||
-                // every XCD slot cleared: a recycled block must not hold a live epoch
-                (e = hipMemset(p->d_err, 0, kErrWords * sizeof(uint32_t))) != hipSuccess ||
-                (e = hipMemcpy(p->d_err, std::array<uint32_t, 2>{0u, kWaitLimitDefault}.data(),
-                               2 * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess)
-                return fail(e, "stripe work list");
-            if ((e = hipMemcpy(p->d_pairs, p->h_pairs.data(), n_pairs * sizeof(NwPairDesc),
-                               hipMemcpyHostToDevice)) != hipSuccess)
-                return fail(e, "hipMemcpy(pairs)");
-        }
+    if (p->mask_bytes) HIP_TRY(p->own.alloc(&p->d_mask, p->mask_bytes + 64));
+    if (!p->work.empty()) {  // column stripes: work list, progress counters, error words
+        const size_t nb = p->work.size() * sizeof(Word2);
+        HIP_TRY(p->own.alloc(&p->d_work, nb));
+        HIP_TRY(hipMemcpy(p->d_work, p->work.data(), nb, hipMemcpyHostToDevice));
+        HIP_TRY(p->own.alloc(&p->d_prog, p->n_prog * sizeof(uint32_t)));
+        HIP_TRY(p->own.alloc(&p->d_err, kErrWords * sizeof(uint32_t)));
+        // every XCD slot cleared: a recycled block must not hold a live epoch
+        HIP_TRY(hipMemset(p->d_err, 0, kErrWords * sizeof(uint32_t)));
+        const uint32_t err01[2] = {0u, kWaitLimitDefault};
+        HIP_TRY(hipMemcpy(p->d_err, err01, sizeof err01, hipMemcpyHostToDevice));
     }
     clk.mark("plan: mask+work");
-    if (soff && (e = dev_alloc(p->ctx, (void **)&p->d_scratch, soff * sizeof(int2))) != hipSuccess)
-        return fail(e, "hipMalloc(scratch)");
-    p->ops_words = ooff;
-    if (ooff && (e = dev_alloc(p->ctx, (void **)&p->d_ops, ooff * sizeof(uint32_t))) != hipSuccess)
-        return fail(e, "hipMalloc(op stream)");
-    // table fills (4-bit codes; full codes in 16-lane groups): a bail word per variant
-    if ((p->var_count[kNarrowVariant] && p->nib[kNarrowVariant]) ||
-        (p->var_count[kPacked16x10] && p->nib[kPacked16x10]) ||
-        (p->full_codes && (p->var_count[kPacked16x16] || p->var_count[kPacked16x10]))) {
-        if ((e = dev_alloc(p->ctx, (void **)&p->d_bail[0], kBailBytes)) != hipSuccess ||
-            (e = hipMemset(p->d_bail[0], 0, kBailBytes)) != hipSuccess)
-            return fail(e, "table fill bail words");
+    if (p->scratch_elems) HIP_TRY(p->own.alloc(&p->d_scratch, p->scratch_elems * sizeof(int2)));
+    if (p->ops_words) HIP_TRY(p->own.alloc(&p->d_ops, p->ops_words * sizeof(uint32_t)));
+    if (p->bail) {
+        HIP_TRY(p->own.alloc(&p->d_bail[0], kBailBytes));
+        HIP_TRY(hipMemset(p->d_bail[0], 0, kBailBytes));
     }
-    {
-        // Speculative stripe walks: a few long column-stripe pairs walk all
-        // their 256-column stripes at once (nw_traceback_coop_kernel kSpec)
-        // instead of one stripe after another (C4: walk 3.8 ms).  Off with
-        // option nw.spec = 0; nw.spec_passes walk passes (default 3).
-        const int passes = (int)opts[Opt::SpecPasses];
-        const uint32_t nv = p->var_count[kStripeVariant];
-        std::vector<SpecPair> sp;
-        std::vector<uint2> blocks;
-        if (opts[Opt::Spec] != 0 && passes > 0 && nv && nv <= kSpecMaxPairs) {
-            for (uint32_t r = p->var_first[kStripeVariant]; r < p->var_first[kStripeVariant] + nv; ++r) {
-                const NwPairDesc &d = p->h_pairs[r];
-                const uint32_t S = (d.len_q + 255) / 256;
-                if (S < kSpecMinStripes || S > kSpecMaxStripes) continue;
-                sp.push_back(SpecPair{r, S, (uint32_t)blocks.size(), 0});
-                for (uint32_t s = 0; s < S; ++s) blocks.push_back(make_uint2((uint32_t)sp.size() - 1, s));
-            }
-        }
-        if (!sp.empty()) {
-            p->spec_pairs = (uint32_t)sp.size();
-            p->spec_blocks = (uint32_t)blocks.size();
-            p->spec_passes = passes;
-            p->spec_strict = opts[Opt::SpecStrict] != 0;
-            if ((e = dev_alloc(p->ctx, (void **)&p->d_spec_blocks, blocks.size() * sizeof(uint2))) != hipSuccess ||
-                (e = hipMemcpy(p->d_spec_blocks, blocks.data(), blocks.size() * sizeof(uint2),
-                               hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_spec_pairs, sp.size() * sizeof(SpecPair))) != hipSuccess ||
-                (e = hipMemcpy(p->d_spec_pairs, sp.data(), sp.size() * sizeof(SpecPair),
-                               hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_spec_stripes, blocks.size() * sizeof(SpecStripe))) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_spec_ops,
-                               blocks.size() * kSpecOpsCap * sizeof(uint32_t))) != hipSuccess ||
-                (e = dev_alloc(p->ctx, (void **)&p->d_spec_done, n_pairs * sizeof(uint32_t))) != hipSuccess ||
-                (e = hipMemset(p->d_spec_done, 0, n_pairs * sizeof(uint32_t))) != hipSuccess)
-                return fail(e, "speculative walk tables");
-        }
+    if (!p->spec_pair_tab.empty()) {
+        p->spec_pairs = (uint32_t)p->spec_pair_tab.size();
+        p->spec_blocks = (uint32_t)p->spec_block_tab.size();
+        const size_t nb = p->spec_blocks * sizeof(Word2), np = p->spec_pairs * sizeof(SpecPair);
+        HIP_TRY(p->own.alloc(&p->d_spec_blocks, nb));
+        HIP_TRY(hipMemcpy(p->d_spec_blocks, p->spec_block_tab.data(), nb, hipMemcpyHostToDevice));
+        HIP_TRY(p->own.alloc(&p->d_spec_pairs, np));
+        HIP_TRY(hipMemcpy(p->d_spec_pairs, p->spec_pair_tab.data(), np, hipMemcpyHostToDevice));
+        HIP_TRY(p->own.alloc(&p->d_spec_stripes, p->spec_blocks * sizeof(SpecStripe)));
+        HIP_TRY(p->own.alloc(&p->d_spec_ops,
+                             (size_t)p->spec_blocks * kSpecOpsCap * sizeof(uint32_t)));
+        HIP_TRY(p->own.alloc(&p->d_spec_done, n_pairs * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(p->d_spec_done, 0, n_pairs * sizeof(uint32_t)));
     }
-    *out = p;
+    *out = p.release();
     return SALN_OK;
 }
 
@@ -665,7 +397,7 @@ int saln_nw_plan_set_timing(saln_nw_plan *p, int enable) {
     constexpr size_t kEventSets = 64;
     while (p->timing && p->ev_pool.size() < kEventSets) {
         std::array<hipEvent_t, 4> e4{};
-        for (auto &e : e4) HIP_TRY(hipEventCreate(&e));
+        for (auto &e : e4) HIP_TRY(p->own.event(&e));
         p->ev_pool.push_back(e4);
     }
     return SALN_OK;
@@ -729,7 +461,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
     if (p->timing) {
         if (p->ev_used == p->ev_pool.size()) {
             std::array<hipEvent_t, 4> e4{};
-            for (auto &e : e4) HIP_TRY(hipEventCreate(&e));
+            for (auto &e : e4) HIP_TRY(p->own.event(&e));
             p->ev_pool.push_back(e4);
         }
         ev = p->ev_pool[p->ev_used++].data();
@@ -845,12 +577,11 @@ int saln_nw_plan_set_async(saln_nw_plan *p, int enable) {
     if (!p) return SALN_E_INVALID;
     HIP_TRY(hipSetDevice(p->ctx->device));
     if (enable && !p->d_mask2 && p->mask_bytes) {
-        HIP_TRY(dev_alloc(p->ctx, (void **)&p->d_mask2, p->mask_bytes + 64));
-        HIP_TRY(dev_alloc(p->ctx, (void **)&p->d_endh2, p->n_pairs * sizeof(int32_t)));
-        if (p->ops_words)
-            HIP_TRY(dev_alloc(p->ctx, (void **)&p->d_ops2, p->ops_words * sizeof(uint32_t)));
+        HIP_TRY(p->own.alloc(&p->d_mask2, p->mask_bytes + 64));
+        HIP_TRY(p->own.alloc(&p->d_endh2, p->n_pairs * sizeof(int32_t)));
+        if (p->ops_words) HIP_TRY(p->own.alloc(&p->d_ops2, p->ops_words * sizeof(uint32_t)));
         if (p->d_bail[0]) {
-            HIP_TRY(dev_alloc(p->ctx, (void **)&p->d_bail[1], kBailBytes));
+            HIP_TRY(p->own.alloc(&p->d_bail[1], kBailBytes));
             HIP_TRY(hipMemset(p->d_bail[1], 0, kBailBytes));
         }
     }

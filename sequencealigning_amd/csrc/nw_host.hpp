@@ -8,6 +8,7 @@
 
 #include "host_common.hpp"
 #include "nw_common.hpp"
+#include "nw_plan_layout.hpp"
 #include "nw_policy.hpp"
 
 namespace saln {
@@ -66,9 +67,6 @@ hipError_t launch_next_event(const NwPairDesc *pairs, uint32_t n, const uint8_t 
 hipError_t launch_cigar_compact(const saln_nw_result *res, const uint64_t *src_off,
                                 const uint64_t *dst_off, const uint32_t *src, uint32_t *dst,
                                 uint64_t n, hipStream_t stream);
-// column-stripe pairs: boundary columns allocated per pair (the row fill cuts
-// each 256-column chunk into up to 4 stripes)
-constexpr uint32_t kStripeSubMax = 4;
 hipError_t launch_score_results(const NwPairDesc *pairs, uint32_t first, uint32_t n,
                                 const int32_t *end_h, saln_nw_result *results, Scoring sc,
                                 hipStream_t stream);
@@ -121,8 +119,6 @@ hipError_t launch_avsa_boundary(const uint64_t *q_off, const uint64_t *d_off,
 hipError_t launch_avsa_scatter(const saln_nw_result *res, const uint32_t *q_ids, uint32_t nq,
                                const uint32_t *d_ids, uint64_t n, uint32_t nq_total, int2 *out,
                                hipStream_t stream);
-
-Scoring scoring_or_default(const saln_nw_scoring *s);
 
 // Host copy of one pair's parent codes: LB-byte segments, row-major, with
 // row stride rs and block stride bs (nw_common.hpp Geom).

@@ -1230,3 +1230,47 @@ def test_score_only_plan_refuses_walk_codes(saln, oracle):
         assert bool(got[-1, -1] & 8) == ((dm[-1, -1] & 1) == 0), (k, "argM")
 
     _score_only_toggle(saln, queries, dbs, False, lambda p, k: p.walk_codes(k), want)
+
+
+def test_plan_destroy_and_recreate_with_every_block(saln):
+    """A plan that owns every kind of block (stripe work list and progress
+    words, speculative tables, table-fill bail words, the second workspace of
+    set_async) is destroyed after pipelined executes and created again: the
+    blocks come back from the context cache, and the second plan's results
+    must equal a synchronous plan's word for word."""
+    import torch
+    from sequencealigning_amd import synth
+    lq = np.array([1300, 150, 2000, 150, 1700, 150, 150, 1999], np.uint64)
+    ld = np.array([300, 290, 310, 300, 280, 150, 300, 305], np.uint64)
+    n = len(lq)
+    qo = np.zeros(n + 1, np.uint64); qo[1:] = np.cumsum(lq)
+    do = np.zeros(n + 1, np.uint64); do[1:] = np.cumsum(ld)
+    pairs = np.stack([np.arange(n), np.arange(n)], 1)
+    dq = torch.from_numpy(synth.random_bases(71, int(qo[-1]))).cuda()
+    dd = torch.from_numpy(synth.random_bases(72, int(do[-1]))).cuda()
+
+    def buffers(plan):
+        return (torch.zeros(n * 4, dtype=torch.int32, device="cuda"),
+                torch.zeros(max(1, plan.cigar_words), dtype=torch.int32, device="cuda"))
+
+    sync_plan = saln.NwPlan(qo, do, pairs=pairs)
+    assert {sync_plan.pair_path(k).variant for k in range(n)} == {3, 4}  # stripes, 8 x 19 table fill
+    want = buffers(sync_plan)
+    sync_plan.execute(dq, dd, *want)
+    assert sync_plan.status() == 0
+    got = None
+    for _ in range(2):
+        pipe = saln.NwPlan(qo, do, pairs=pairs)
+        pipe.set_async(True)
+        outs = [buffers(pipe), buffers(pipe)]
+        for r, c in outs:
+            pipe.execute(dq, dd, r, c)
+        pipe.sync()
+        assert pipe.status() == 0
+        got = outs
+        pipe.close()
+    torch.cuda.synchronize()
+    for r, c in got:
+        assert torch.equal(r, want[0])
+        assert torch.equal(c, want[1])
+    sync_plan.close()
