@@ -780,8 +780,9 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
  *    'I' and stops, on column 0 with i > 0 one run of i 'D' and stops, else
  *    the next state is the first of M, I, D equal to M(i,j) - s(i,j).
  *    q_begin = db_begin = 0 always; the '=', 'X', 'I' lengths sum to q_end
- *    and the '=', 'X', 'D' lengths to db_end.  X-drop / Z-drop termination is
- *    not part of it: every cell is computed.
+ *    and the '=', 'X', 'D' lengths to db_end.  Every cell is computed; the
+ *    X-drop form, which prunes cells and stops the fill early, is
+ *    saln_ends_free_xdrop_align_batch ("X-drop extension", below).
  * The walk's choice among co-optimal paths is fixed.  In M at (i,j): emit
  * '=' or 'X', v = M(i,j) - s(i,j), go to (i-1,j-1); local stops when v == 0,
  * semi-global on reaching column 0, overlap on reaching row 0 or column 0;
@@ -801,7 +802,7 @@ int saln_wfa_affine_plan_geometry(const saln_wfa_penalties *pen, const uint64_t 
 typedef struct {
     int32_t score, status;            /* SALN_OK | SALN_TRACE_CAP | SALN_INTERNAL (replay only) */
     int32_t q_begin, q_end, db_begin, db_end;   /* begins -1 when no walk ran */
-    uint32_t cigar_len, reserved;
+    uint32_t cigar_len, reserved;     /* reserved: 0; saln_ends_free_xdrop_*: the fill's steps (below) */
 } saln_ends_free_result;              /* 32 bytes */
 
 /* Pair conventions and argument errors as saln_wfa_affine_align_batch (NULL
@@ -855,6 +856,65 @@ int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes)
  * 64 x 8, 64 x 16: the smallest that holds the query).  SALN_E_INVALID above
  * 1,024 columns.  The launch code asks the same function. */
 int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols_per_lane);
+
+/* X-drop extension: SALN_MODE_EXTEND with one more rule and a parameter
+ * xdrop = X >= 0.  Borders, recurrences, tie rules and the walk are
+ * extension's.  Every cell (i,j), 0 <= i <= m, 0 <= j <= n, also carries
+ * B(i,j): the largest P of an unpruned cell in its dominance region
+ * {(i',j') : i' <= i, j' <= j}.
+ *  - (0,0) has P = B = 0 and is never pruned.
+ *  - Every other cell computes M, I, D by extension's recurrences from its
+ *    neighbours' values after pruning; P = max(M, I, D) and Bin =
+ *    max(B(i-1,j), B(i,j-1)), a B outside the matrix being -infinity.
+ *  - The cell is pruned iff P < Bin - X (strict).  A pruned cell has M = I =
+ *    D = -infinity for every successor, and B = Bin.  An unpruned cell keeps
+ *    its values, and B = max(Bin, P).
+ * B obeys the dependencies of the recurrence, so the tables, and with them the
+ * record and the words, depend on nothing but the pair, the scoring and X:
+ * not on the order in which cells are computed, not on the class geometry.
+ * Consequences:
+ *  - Row 0 and column 0 have closed forms: (0,j) is unpruned iff o + j e >=
+ *    -X, (i,0) iff o + i e >= -X, and B is 0 there.
+ *  - Score and end cell are extension's rule over the unpruned cells: max(0,
+ *    max M(i,j), i, j >= 1), the smallest i, then the smallest j.  A pruned
+ *    cell's M lies below Bin - X, hence below an unpruned M or 0: it never
+ *    wins or ties.
+ *  - The walk never reads a pruned cell: an unpruned cell's chosen
+ *    predecessor holds a finite value.
+ *  - The score is monotone in X and never above extension's.  With X >=
+ *    2 (n + m + 2) max|parameter| nothing real is pruned: records (but
+ *    `reserved`) and words equal saln_ends_free_align_batch's under
+ *    SALN_MODE_EXTEND.
+ *  - Early stop.  With L the last row that holds an unpruned cell, every cell
+ *    below row L is pruned, and so is everything behind any fully pruned front
+ *    of the fill; the fill leaves a pair as soon as its front is pruned.
+ * Domain: xdrop >= 0, and the range guard becomes (n + m + 2) *
+ * max|parameter| + xdrop < 2^30; outside it the batch is SALN_E_INVALID with a
+ * message.  Limits (1,024 columns, 65,000 rows, a message naming the limit),
+ * trace budget, chunking and SALN_TRACE_CAP are saln_ends_free_align_batch's:
+ * codes stay sized for all m rows.  Arguments are validated before the device
+ * is touched.
+ * `reserved` of these entry points' records is a diagnostic: the number of
+ * row-loop steps the pair's group of lanes ran.  Unlike the rest of the record
+ * it depends on the class geometry (G lanes, saln_ends_free_pair_geometry):
+ * reserved <= min(m, L) + G, the group voting after every step (G - 1 steps
+ * of skew and the vote's one); 0 for a pair without a query column.  A plain
+ * fill runs m + G - 1 steps.
+ * The entry points are their plain counterparts without `mode` and with
+ * xdrop; saln_ends_free_execute / _plan_destroy and saln_ends_free_aln_count /
+ * _get / _free serve them unchanged.  The chunked fill and the tiled replay
+ * have no X-drop form. */
+int saln_ends_free_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                     uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                     uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                     uint64_t n_pairs, const saln_nw_scoring *scoring, int32_t xdrop,
+                                     uint64_t trace_budget_bytes, int want_cigar,
+                                     saln_ends_free_aln **out);
+int saln_ends_free_xdrop_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                     const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                     const uint32_t *pair_db, uint64_t n_pairs,
+                                     const saln_nw_scoring *scoring, int32_t xdrop,
+                                     saln_ends_free_plan **out);
 
 /* Pairs of any length (ends_free_long_kernels.hip, ends_free_long_host.cpp).
  * saln_ends_free_long_align_batch is saln_ends_free_align_batch without the
@@ -997,6 +1057,18 @@ int saln_ends_free_sub_plan_create(saln_context *ctx, const uint64_t *q_off, uin
                                    const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
                                    const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
                                    const saln_sub_matrix *matrix, saln_ends_free_plan **out);
+/* The X-drop extension (above) under a matrix. */
+int saln_ends_free_sub_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                         uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                         uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                         uint64_t n_pairs, const saln_sub_matrix *matrix, int32_t xdrop,
+                                         uint64_t trace_budget_bytes, int want_cigar,
+                                         saln_ends_free_aln **out);
+int saln_ends_free_sub_xdrop_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                         const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                         const uint32_t *pair_db, uint64_t n_pairs,
+                                         const saln_sub_matrix *matrix, int32_t xdrop,
+                                         saln_ends_free_plan **out);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

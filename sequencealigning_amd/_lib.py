@@ -155,6 +155,8 @@ EXPORTS = [
     "saln_ends_free_replay_align_batch", "saln_ends_free_replay_bytes",
     "saln_sub_matrix_check", "saln_ends_free_sub_align_batch", "saln_ends_free_sub_long_align_batch",
     "saln_ends_free_sub_replay_align_batch", "saln_ends_free_sub_plan_create",
+    "saln_ends_free_xdrop_align_batch", "saln_ends_free_sub_xdrop_align_batch",
+    "saln_ends_free_xdrop_plan_create", "saln_ends_free_sub_xdrop_plan_create",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -331,6 +333,11 @@ def lib() -> C.CDLL:
         sub_plan = list(L.saln_ends_free_plan_create.argtypes)
         sub_plan[9] = C.POINTER(SubMatrix)
         L.saln_ends_free_sub_plan_create.argtypes = sub_plan
+        # the X-drop forms: no mode, xdrop after the scoring
+        for batch, plan, name in ((L.saln_ends_free_align_batch.argtypes, L.saln_ends_free_plan_create.argtypes, "saln_ends_free_xdrop_"),
+                                  (sub_batch, sub_plan, "saln_ends_free_sub_xdrop_")):
+            getattr(L, name + "align_batch").argtypes = list(batch[:10]) + [batch[11], C.c_int32] + list(batch[12:])
+            getattr(L, name + "plan_create").argtypes = list(plan[:8]) + [plan[9], C.c_int32, plan[10]]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

@@ -187,11 +187,14 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
 // ld_max rows.  mode: SALN_MODE_LOCAL, _SEMI_GLOBAL, _OVERLAP or _EXTEND (the
 // host has checked it).  codes == nullptr: score only.  end_state (with codes): the
 // state of each pair's end cell (0 M, 1 I), indexed like results; overlap's
-// walk takes it from the end cell's own code instead.
+// walk takes it from the end cell's own code instead.  xdrop: kEfNoXdrop, or
+// X >= 0 with SALN_MODE_EXTEND: the X-drop instances (saln_ends_free_xdrop_*),
+// which also leave their row-loop steps in the records' `reserved`.
+constexpr int32_t kEfNoXdrop = -1;
 hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
                           const uint8_t *sub, uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
-                          hipStream_t s);
+                          hipStream_t s, int32_t xdrop = kEfNoXdrop);
 // Chunked fill of pairs[first .. first + count) (any lengths): `slots` waves,
 // each with slot_rows (>= the longest db) 8-byte entries of bnd, taking pairs
 // from *counter, which the caller has zeroed on the stream.

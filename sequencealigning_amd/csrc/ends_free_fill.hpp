@@ -1,7 +1,8 @@
 // The steps of the ends-free fill: row 0, a lane's row of K cells (the Gotoh
 // recurrence, the trace code, the three modes' end-cell trackers), the code
 // store, overlap's last row, and the group's end cell with its record.
-// ef_fill_kernel (ends_free_kernels.hip) is built from all of them.
+// ef_fill_kernel and ef_xdrop_fill_kernel (ends_free_kernels.hip) are built
+// from all of them.
 // ef_fill_long_kernel (ends_free_long_kernels.hip) uses those outside its
 // loops (ef_overlap_end, ef_reduce_best, ef_store_end) and keeps its own row 0,
 // row and chunk code: built from ef_row0 / ef_row its step loop compiled to
@@ -11,6 +12,10 @@
 // A lane holds K consecutive query columns col0+1 .. col0+K (col0 absolute) in
 // registers: qc their bases, Hp = P(r-1, j), Dn = D(r, j).  kMode is
 // SALN_MODE_LOCAL, SALN_MODE_SEMI_GLOBAL, SALN_MODE_OVERLAP or SALN_MODE_EXTEND.
+// kXdrop (extend only; include/saln.h, "X-drop extension"): every cell also
+// carries B, the largest P of an unpruned cell of its dominance region, and a
+// cell whose P lies more than X below max(B above, B left) is pruned: it hands
+// exactly kEfNeg to its successors.  EfDrop holds what a lane keeps for it.
 #pragma once
 #include "ends_free_dev.hpp"
 
@@ -36,6 +41,22 @@ __device__ __forceinline__ EfBest ef_best_row0(uint32_t lq, int32_t o, int32_t e
     else
         return {0, 0u, 0u};
 }
+
+// What kXdrop adds to a lane.  B is 0 on row 0 and in column 0 (the origin is
+// the only cell there with P >= 0), so Bp starts at 0 and lane 0 takes 0.  A
+// pad column starts at kEfPadB instead: every value lies below kEfPadB - X
+// (the range guard), so a pad cell is always pruned, hands kEfPadB on to the
+// pad cells right of it and below it, and never counts as alive: the vote
+// needs no mask for the pads, as the tracker needs none.
+constexpr int32_t kEfPadB = 1 << 30;
+template <int K>
+struct EfDrop {
+    int32_t Bp[K];  // B(r-1, j) of my columns
+    int32_t inB;    // B(r, col0), from the left neighbour
+    int32_t pubB;   // B(r, col0+K), for the right neighbour
+    int32_t X;
+    bool alive;     // left by ef_row: a cell of its row was not pruned
+};
 
 // kSub (scoring under a substitution matrix, ends_free.hpp): the workgroup's
 // copy in LDS of the batch's block `sub`, code[] then the score rows; nullptr
@@ -69,10 +90,12 @@ __device__ __forceinline__ const int8_t *ef_sub_row(const uint8_t *lds, uint32_t
 
 // Row 0 of the columns behind col0.  Returns hd = P(0, col0).  kSub: qc holds
 // the columns' symbols (sub: the block in LDS) and kEfSubPad in pad columns.
-template <int K, int kMode, bool kSub = false>
+// kXdrop: (0, j) is pruned iff o + j e < -X (B is 0 all along row 0).
+template <int K, int kMode, bool kSub = false, bool kXdrop = false>
 __device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32_t lq, uint32_t col0,
                                            int32_t o, int32_t e, uint32_t (&qc)[K], int32_t (&Hp)[K],
-                                           int32_t (&Dn)[K], const uint8_t *sub = nullptr) {
+                                           int32_t (&Dn)[K], const uint8_t *sub = nullptr, int32_t X = 0) {
+    static_assert(!kXdrop || kMode == SALN_MODE_EXTEND, "X-drop is extension's");
     // extension's row 0 is semi-global's: P(0, j) = I(0, j), D(1, j) = -inf
     constexpr bool kSemi = kMode == SALN_MODE_SEMI_GLOBAL || kMode == SALN_MODE_EXTEND;
     constexpr bool kOverlap = kMode == SALN_MODE_OVERLAP;
@@ -85,10 +108,13 @@ __device__ __forceinline__ int32_t ef_row0(const uint8_t *__restrict__ q, uint32
             qc[k] = j <= lq ? (uint32_t)q[j - 1] : 0x100u;  // pad columns match nothing
         // semi-global and extend P(0, j) = I(0, j) = o + j e; local and overlap P = 0
         Hp[k] = !kSemi ? 0 : j <= lq ? o + (int32_t)j * e : kEfNeg;
+        if constexpr (kXdrop) Hp[k] = Hp[k] < -X ? kEfNeg : Hp[k];
         // D(1, j): M(0, j) and D(0, j) are -inf; overlap opens it from M(0, j) = 0
         Dn[k] = kOverlap ? o + e : kEfNeg;
     }
-    return !kSemi || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
+    const int32_t h0 = !kSemi || col0 == 0 ? 0 : col0 <= lq ? o + (int32_t)col0 * e : kEfNeg;
+    if constexpr (kXdrop) return h0 < -X ? kEfNeg : h0;
+    return h0;
 }
 
 // A lane's K codes of one row (4 bits per cell), column col0 + 1 in the low
@@ -139,12 +165,23 @@ __device__ __forceinline__ void ef_store_codes(uint8_t *to, const EfCodes<K> &c)
 // induction.  Nothing of this wraps: every pad value is at least
 // kEfNeg - (m + 3) max|parameter| (D(i, j) >= D(1, j) + (i - 1) e bounds P
 // from below in every column), which the range guard keeps above -2^31.
-template <int K, int kMode, bool kCodes, bool kSub = false>
+//
+// kXdrop (xd): per cell Bin = max(B(r-1, j), B(r, j-1)); the cell is pruned iff
+// P < Bin - X, and then its P, the I it hands right and the D it hands down
+// are exactly kEfNeg; B(r, j) = max(Bin, outgoing P).  The tracker still needs
+// no mask: a pruned cell's M is below Bin - X, and Bin is the P of an unpruned
+// cell, which is at most a live M or 0 by the argument above.  Its code is
+// stored but never read (a live cell's chosen predecessor holds a real value).
+// Everything derived from kEfNeg is at most kEfNeg + (n + m + 2) max|parameter|,
+// which the range guard (with X in it) keeps below -X <= Bin - X: pruned, and
+// reset to kEfNeg, so nothing accumulates.
+template <int K, int kMode, bool kCodes, bool kSub = false, bool kXdrop = false>
 __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, int32_t inF, int32_t inH,
                                        const EfScoring &sc, uint32_t k_end, uint32_t r,
                                        int32_t (&Hp)[K], int32_t (&Dn)[K], int32_t &hd, int32_t &pubF,
                                        int32_t &pubH, EfBest &best, EfCodes<K> &codes,
-                                       const uint8_t *sub = nullptr) {
+                                       const uint8_t *sub = nullptr, EfDrop<K> *xd = nullptr) {
+    static_assert(!kXdrop || kMode == SALN_MODE_EXTEND, "X-drop is extension's");
     constexpr bool kLocal = kMode == SALN_MODE_LOCAL, kOverlap = kMode == SALN_MODE_OVERLAP;
     constexpr bool kEveryM = kLocal || kMode == SALN_MODE_EXTEND;  // the tracker over every M
     const int32_t o = sc.open, e = sc.extend;
@@ -152,6 +189,9 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
     if constexpr (kSub) trow = ef_sub_row(sub, dch);
     int32_t F = inF;
     int32_t Msel = kEfNeg, Isel = kEfNeg;
+    int32_t Bl = 0;  // kXdrop: B(r, j-1)
+    bool alive = false;
+    if constexpr (kXdrop) Bl = xd->inB;
     if constexpr (kCodes) {
 #pragma unroll
         for (int n = 0; n < (K + 7) / 8; ++n) codes.w[n] = 0;
@@ -166,7 +206,16 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
         const int32_t M = ef_add(hd, s);
         const int32_t I = F, D = Dn[k];
         const int32_t P3 = max(M, max(I, D));
-        const int32_t P = kLocal ? max(P3, 0) : P3;
+        int32_t P = kLocal ? max(P3, 0) : P3;
+        bool cut = false;
+        if constexpr (kXdrop) {
+            const int32_t Bin = max(xd->Bp[k], Bl);
+            cut = P3 < Bin - xd->X;
+            P = cut ? kEfNeg : P3;
+            Bl = max(Bin, P);
+            xd->Bp[k] = Bl;
+            alive = alive || !cut;
+        }
         const int32_t tO = ef_add(M, o);
         if constexpr (kCodes) {
             uint32_t c = M == P3 ? 0u : I == P3 ? 1u : 2u;
@@ -190,12 +239,20 @@ __device__ __forceinline__ void ef_row(const uint32_t (&qc)[K], uint32_t dch, in
         }
         F = ef_add(max(tO, I), e);      // I(r, j+1)
         Dn[k] = ef_add(max(tO, D), e);  // D(r+1, j)
+        if constexpr (kXdrop) {
+            F = cut ? kEfNeg : F;
+            Dn[k] = cut ? kEfNeg : Dn[k];
+        }
         hd = Hp[k];
         Hp[k] = P;
     }
     hd = inH;
     pubF = F;
     pubH = Hp[K - 1];
+    if constexpr (kXdrop) {
+        xd->pubB = Bl;
+        xd->alive = alive;
+    }
     if constexpr (kOverlap) {
         const bool b = Msel > best.v;  // the smallest row wins a tie
         best.v = b ? Msel : best.v;
@@ -243,18 +300,21 @@ __device__ __forceinline__ void ef_overlap_end(bool owner, uint32_t lq, uint32_t
     j = row ? rbest_j : lq;
 }
 
-// The pair's record: score and end cell; the walk fills in the rest.
+// The pair's record: score and end cell; the walk fills in the rest.  steps:
+// what `reserved` reports (the X-drop fill's row-loop steps; 0 elsewhere).
 template <bool kCodes>
 __device__ __forceinline__ void ef_store_end(saln_ends_free_result *__restrict__ results,
                                              uint8_t *__restrict__ end_state, uint32_t out, int32_t score,
-                                             uint32_t db_end, uint32_t q_end, uint32_t state) {
+                                             uint32_t db_end, uint32_t q_end, uint32_t state,
+                                             uint32_t steps = 0) {
     saln_ends_free_result res;
     res.score = score;
     res.status = SALN_OK;
     res.q_begin = res.db_begin = -1;
     res.q_end = (int32_t)q_end;
     res.db_end = (int32_t)db_end;
-    res.cigar_len = res.reserved = 0;
+    res.cigar_len = 0;
+    res.reserved = steps;
     results[out] = res;
     if constexpr (kCodes) end_state[out] = (uint8_t)state;
 }
@@ -269,7 +329,8 @@ template <int G, int kMode, bool kCodes>
 __device__ __forceinline__ void ef_reduce_best(int lane, bool owner, int32_t v, uint32_t i, uint32_t j,
                                                uint32_t state, uint32_t lq,
                                                saln_ends_free_result *__restrict__ results,
-                                               uint8_t *__restrict__ end_state, uint32_t out) {
+                                               uint8_t *__restrict__ end_state, uint32_t out,
+                                               uint32_t steps = 0) {
     if constexpr (kMode == SALN_MODE_SEMI_GLOBAL) {
         if (owner) ef_store_end<kCodes>(results, end_state, out, v, i, lq, state);
     } else {
@@ -284,7 +345,8 @@ __device__ __forceinline__ void ef_reduce_best(int lane, bool owner, int32_t v, 
             i = take ? oi : i;
             j = take ? oj : j;
         }
-        if (lane == 0) ef_store_end<kCodes>(results, end_state, out, v, v > 0 ? i : 0u, v > 0 ? j : 0u, 0u);
+        if (lane == 0)
+            ef_store_end<kCodes>(results, end_state, out, v, v > 0 ? i : 0u, v > 0 ? j : 0u, 0u, steps);
     }
 }
 

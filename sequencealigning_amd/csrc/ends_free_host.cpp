@@ -112,9 +112,25 @@ int make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::
     return SALN_OK;
 }
 
+// An X-drop call's X (kEfNoXdrop: none): >= 0, extension only, the class fills only.
+int check_xdrop(int32_t xdrop, int32_t mode, bool long_ok) {
+    if (xdrop == kEfNoXdrop) return SALN_OK;
+    if (xdrop < 0) {
+        set_error("ends_free: xdrop " + std::to_string(xdrop) + " is negative (X >= 0)");
+        return SALN_E_INVALID;
+    }
+    if (mode != SALN_MODE_EXTEND || long_ok) {
+        set_error("ends_free: X-drop is part of SALN_MODE_EXTEND under the class fills only");
+        return SALN_E_INVALID;
+    }
+    return SALN_OK;
+}
+
 // The engine's limits for one pair (lengths, int32 range of the values).
-// long_ok: the chunked fill takes the lengths the classes refuse.
-int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs, bool long_ok = false) {
+// long_ok: the chunked fill takes the lengths the classes refuse.  xdrop (an
+// X-drop call's X, else 0) is part of the range guard: everything derived from
+// -infinity must stay below -X.
+int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs, bool long_ok = false, uint64_t xdrop = 0) {
     if (lq > kEfMaxQ && !long_ok) {
         set_error("ends_free: a query of " + std::to_string(lq) + " columns is above the limit of " +
                   std::to_string(kEfMaxQ) + " (one chunk of the lane fill); "
@@ -127,9 +143,9 @@ int check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs, bool long_ok = false)
                   "saln_ends_free_long_align_batch takes longer pairs");
         return SALN_E_INVALID;
     }
-    if ((lq + ld + 2) * max_abs >= (1ull << 30)) {
-        set_error("ends_free: (len_q + len_db + 2) * max|scoring parameter| reaches 2^30: the "
-                  "scores could leave the engine's int32 range");
+    if ((lq + ld + 2) * max_abs + xdrop >= (1ull << 30)) {
+        set_error(std::string("ends_free: (len_q + len_db + 2) * max|scoring parameter|") +
+                  (xdrop ? " + xdrop" : "") + " reaches 2^30: the scores could leave the engine's int32 range");
         return SALN_E_INVALID;
     }
     return SALN_OK;
@@ -151,14 +167,14 @@ uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok, uint32_t tile_rows) 
 
 int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
                 const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, uint64_t max_abs,
-                std::vector<EfPair> *out, bool long_ok = false) {
+                std::vector<EfPair> *out, bool long_ok = false, int32_t xdrop = kEfNoXdrop) {
     out->resize(n_pairs);
     const PairIndex pairs{pair_q, pair_db, n_q, n_db};
     for (uint64_t k = 0; k < n_pairs; ++k) {
         uint64_t qi, di;
         if (!pairs.at(k, &qi, &di)) return SALN_E_INVALID;
         const uint64_t lq = q_off[qi + 1] - q_off[qi], ld = db_off[di + 1] - db_off[di];
-        const int rc = check_pair(lq, ld, max_abs, long_ok);
+        const int rc = check_pair(lq, ld, max_abs, long_ok, xdrop == kEfNoXdrop ? 0 : (uint64_t)xdrop);
         if (rc != SALN_OK) return rc;
         EfPair p{};
         p.q_off = q_off[qi];
@@ -173,21 +189,22 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
 }
 
 // The fills of `pairs` (device copy d_pairs, in plan_launches' order).  ws:
-// the chunked fill's workspace (launches of kEfLongClass need one).
+// the chunked fill's workspace (launches of kEfLongClass need one).  xdrop:
+// kEfNoXdrop or the class fills' X (check_xdrop: no launch is chunked then).
 int run_fills(const std::vector<Launch> &launches, int32_t mode, const EfPair *d_pairs,
               const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, const uint8_t *d_sub,
               uint8_t *d_codes, uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
-              EfLongWorkspace *ws = nullptr) {
+              EfLongWorkspace *ws = nullptr, int32_t xdrop = kEfNoXdrop) {
     for (const Launch &l : launches) {
         if (l.cls == kEfLongClass) {
-            if (!ws) return SALN_E_INVALID;
+            if (!ws || xdrop != kEfNoXdrop) return SALN_E_INVALID;
             const int rc = ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
                                         d_codes, d_end_state, d_results, s);
             if (rc != SALN_OK) return rc;
             continue;
         }
         HIP_TRY(launch_ef_fill(l.cls, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
-                               d_codes, d_end_state, d_results, s));
+                               d_codes, d_end_state, d_results, s, xdrop));
     }
     return SALN_OK;
 }
@@ -198,6 +215,7 @@ struct saln_ends_free_plan {
     saln_context *ctx = nullptr;
     EfScoring sc{};
     int32_t mode = SALN_MODE_LOCAL;
+    int32_t xdrop = kEfNoXdrop;
     uint64_t n = 0;
     std::vector<Launch> launches;
     DevBuf d_pairs, d_sub;  // d_sub: the matrix's block (empty: scalar scoring)
@@ -289,12 +307,32 @@ int saln_ends_free_sub_plan_create(saln_context *ctx, const uint64_t *q_off, uin
                           EfScoreSrc::of(matrix), out);
 }
 
+int saln_ends_free_xdrop_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                     const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                     const uint32_t *pair_db, uint64_t n_pairs,
+                                     const saln_nw_scoring *scoring, int32_t xdrop,
+                                     saln_ends_free_plan **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;  // negative: refused with a message
+    return ef_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, SALN_MODE_EXTEND,
+                          EfScoreSrc::of(scoring), out, xdrop);
+}
+
+int saln_ends_free_sub_xdrop_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                         const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                         const uint32_t *pair_db, uint64_t n_pairs,
+                                         const saln_sub_matrix *matrix, int32_t xdrop,
+                                         saln_ends_free_plan **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;
+    return ef_plan_create(ctx, q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, SALN_MODE_EXTEND,
+                          EfScoreSrc::of(matrix), out, xdrop);
+}
+
 }  // extern "C"
 
 int saln::ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off,
                          uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
                          uint64_t n_pairs, int32_t mode, const EfScoreSrc &scoring,
-                         saln_ends_free_plan **out) {
+                         saln_ends_free_plan **out, int32_t xdrop) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     auto p = std::make_unique<saln_ends_free_plan>();
@@ -304,12 +342,14 @@ int saln::ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     uint64_t max_abs = 0;
     std::vector<uint8_t> block;
     int rc = check_mode(mode);
+    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, false);
     if (rc == SALN_OK) rc = make_scoring(scoring, &p->sc, &max_abs, &block);
     std::vector<EfPair> pairs;
     if (rc == SALN_OK)
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &pairs);
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &pairs, false, xdrop);
     if (rc != SALN_OK) return rc;
     p->mode = mode;
+    p->xdrop = xdrop;
     p->n = n_pairs;
     plan_launches(&pairs, &p->launches);
     HIP_TRY(hipSetDevice(ctx->device));
@@ -334,7 +374,7 @@ int saln_ends_free_execute(saln_ends_free_plan *p, const uint8_t *d_q_seq, const
     hipStream_t s = resolve_stream(stream, p->ctx);
     HIP_TRY(hipSetDevice(p->ctx->device));
     return run_fills(p->launches, p->mode, p->d_pairs.as<EfPair>(), d_q_seq, d_db_seq, p->sc,
-                     p->d_sub.as<uint8_t>(), nullptr, nullptr, d_results, s);
+                     p->d_sub.as<uint8_t>(), nullptr, nullptr, d_results, s, nullptr, p->xdrop);
 }
 
 int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
@@ -354,17 +394,19 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
                          const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                          const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
                          int32_t mode, const EfScoreSrc &scoring, uint64_t trace_budget_bytes,
-                         int want_cigar, saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows) {
+                         int want_cigar, saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows,
+                         int32_t xdrop) {
     if (!ctx || !q_off || !db_off || !out || n_pairs > 0xFFFFFFFFull) return SALN_E_INVALID;
     if (!PairIndex{pair_q, pair_db, n_q, n_db}.complete(n_pairs)) return SALN_E_INVALID;
     EfScoring sc{};
     uint64_t max_abs = 0;
     std::vector<uint8_t> block;
     int rc = check_mode(mode);
+    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, long_ok);
     if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs, &block);
     std::vector<EfPair> all;
     if (rc == SALN_OK)
-        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all, long_ok);
+        rc = build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, &all, long_ok, xdrop);
     if (rc != SALN_OK) return rc;
     auto aln = std::make_unique<saln_ends_free_aln>();
     aln->off.assign(n_pairs + 1, 0);
@@ -442,7 +484,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         HIP_TRY(hipMemcpyAsync(d_pairs.p, plain.pairs.data(), plain.pairs.size() * sizeof(EfPair),
                                hipMemcpyHostToDevice, s));
         rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, sub, nullptr, nullptr, results,
-                       s, &ws);
+                       s, &ws, xdrop);
         if (rc != SALN_OK) return rc;
         HIP_TRY(hipStreamSynchronize(s));  // d_pairs and the host vector are reused
     }
@@ -467,7 +509,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
                 launches.pop_back();
             }
         rc = run_fills(launches, mode, d_pairs.as<EfPair>(), sq, sd, sc, sub, d_codes.as<uint8_t>(),
-                       d_state.as<uint8_t>(), results, s, &ws);
+                       d_state.as<uint8_t>(), results, s, &ws, xdrop);
         if (rc != SALN_OK) return rc;
         HIP_TRY(launch_ef_walk(mode, d_pairs.as<EfPair>(), n_walk, sq, sd, d_codes.as<uint8_t>(),
                                d_state.as<uint8_t>(), results, d_words.as<uint32_t>(),
@@ -552,6 +594,30 @@ int saln_ends_free_sub_align_batch(saln_context *ctx, const uint8_t *q_seq, cons
                                    saln_ends_free_aln **out) {
     return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
                           EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out, false);
+}
+
+int saln_ends_free_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                     uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                     uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                     uint64_t n_pairs, const saln_nw_scoring *scoring, int32_t xdrop,
+                                     uint64_t trace_budget_bytes, int want_cigar,
+                                     saln_ends_free_aln **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;  // negative: refused with a message
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs,
+                          SALN_MODE_EXTEND, EfScoreSrc::of(scoring), trace_budget_bytes, want_cigar, out,
+                          false, 0, xdrop);
+}
+
+int saln_ends_free_sub_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                         uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                         uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                         uint64_t n_pairs, const saln_sub_matrix *matrix, int32_t xdrop,
+                                         uint64_t trace_budget_bytes, int want_cigar,
+                                         saln_ends_free_aln **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs,
+                          SALN_MODE_EXTEND, EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out,
+                          false, 0, xdrop);
 }
 
 uint64_t saln_ends_free_aln_count(const saln_ends_free_aln *a) { return a ? a->res.size() : 0; }

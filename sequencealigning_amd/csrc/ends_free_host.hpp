@@ -24,19 +24,24 @@ struct EfScoreSrc {
 // limits and refusals) and saln_ends_free_long_align_batch (long_ok = true:
 // pairs above those limits run the chunked fill) and, with tile_rows != 0,
 // saln_ends_free_replay_align_batch (a chunk holds replay footprints, and the
-// alignments of its chunked-path pairs come from ef_replay_run).
+// alignments of its chunked-path pairs come from ef_replay_run).  xdrop:
+// kEfNoXdrop, or the X of saln_ends_free_xdrop_align_batch (mode
+// SALN_MODE_EXTEND, long_ok false: the class fills' X-drop instances).
 // ends_free_host.cpp.
 int ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                    const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                    const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
                    const EfScoreSrc &scoring, uint64_t trace_budget_bytes, int want_cigar,
-                   saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows = 0);
+                   saln_ends_free_aln **out, bool long_ok, uint32_t tile_rows = 0,
+                   int32_t xdrop = kEfNoXdrop);
 
-// The plan behind saln_ends_free_plan_create and saln_ends_free_sub_plan_create.
+// The plan behind saln_ends_free_plan_create and saln_ends_free_sub_plan_create
+// and, with an xdrop other than kEfNoXdrop, their _xdrop_ forms.
 // ends_free_host.cpp.
 int ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off,
                    uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
-                   int32_t mode, const EfScoreSrc &scoring, saln_ends_free_plan **out);
+                   int32_t mode, const EfScoreSrc &scoring, saln_ends_free_plan **out,
+                   int32_t xdrop = kEfNoXdrop);
 
 // Device workspace of a batch's chunked fills, all on one stream: the boundary
 // slots (grown to the largest launch's need) and the pair counter.

@@ -16,7 +16,8 @@
 // of ends_free_fill.hpp (the chunked fill shares the end cell and keeps a row
 // of its own); this kernel adds the group's db row staged in LDS, lane 0's
 // boundary (column 0: constants, but extend's deletion run o + r e) and the one
-// pass over the rows.
+// pass over the rows.  ef_xdrop_fill_kernel is extension's fill with the X-drop
+// rule and a vote of the group's lanes that ends the pass early.
 //
 // Walk: one pair per lane, from the reported end cell along the 4-bit codes.
 #include <hip/hip_runtime.h>
@@ -107,6 +108,118 @@ __global__ __launch_bounds__(256) void ef_fill_kernel(
     }
     ef_reduce_best<G, kMode, kCodes>(lane, (uint32_t)lane == l_end, best.v, best.i, best_j, best.k, lq,
                                      results, end_state, p.out);
+}
+
+// The group's vote of the X-drop fill: does any of my group's G lanes hold
+// `p`?  G = 16: four groups with four different pairs share the wave, so the
+// wave's ballot is cut down to the group's own 16 bits; lanes of groups that
+// have left the loop are inactive and ballot 0.
+template <int G>
+__device__ __forceinline__ bool ef_group_any(bool p) {
+    const uint64_t b = __ballot(p);
+    if constexpr (G == 64)
+        return b != 0;
+    else
+        return ((b >> (threadIdx.x & 48u)) & 0xFFFFu) != 0;
+}
+
+// The X-drop extension fill (saln_ends_free_xdrop_*):
+// ef_fill_kernel<G, K, SALN_MODE_EXTEND, kCodes, kSub> with the X-drop rule of
+// ef_row (X = xdrop), column 0 pruned by its closed form (o + r e < -X), and a
+// vote after every step: the group leaves the row loop once all its lanes are
+// dead.  A lane is dead when it holds no real column, when its row is past ld,
+// or when every cell of its row (pad cells always are, EfDrop) and the cell
+// left of them, (r, col0), are pruned; a lane with real columns that has not
+// reached row 1 is alive.
+// (r, col0) belongs to the cut because the diagonal step into (r+1, col0+1)
+// comes from it, and its owner, the left neighbour, is one row ahead and no
+// longer votes for it.  Every path from the origin to a cell not yet computed
+// crosses such a cut, so everything still to come is pruned.  The record's
+// `reserved` is the number of steps run.
+// The kernel keeps its own copy of ef_fill_kernel's frame: built from one
+// body shared by both, every existing instance compiled to other code (other
+// registers, other block order), and those instances are not to change.  A
+// change to the frame above is made here too.
+template <int G, int K, bool kCodes, bool kSub>
+__global__ __launch_bounds__(256) void ef_xdrop_fill_kernel(
+    const EfPair *__restrict__ pairs, uint32_t first, uint32_t count,
+    const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds, uint8_t *__restrict__ codes,
+    uint8_t *__restrict__ end_state, saln_ends_free_result *__restrict__ results, EfScoring sc,
+    uint32_t ld_max, const uint8_t *__restrict__ sub, int32_t xdrop) {
+    constexpr int kMode = SALN_MODE_EXTEND;
+    uint8_t *ef_sub = ef_sub_stage<kSub>(sub);  // before any thread leaves
+    const int gpb = (int)blockDim.x / G;
+    const int lane = (int)threadIdx.x % G, grp = (int)threadIdx.x / G;
+    const uint32_t gi = blockIdx.x * (uint32_t)gpb + (uint32_t)grp;
+    if (gi >= count) return;  // whole group (DPP never crosses groups)
+    const EfPair p = pairs[first + gi];
+    const uint32_t lq = p.lq, ld = p.ld;
+    const uint8_t *__restrict__ d = ds + p.d_off;
+    if (lq == 0) {  // no column: score 0 at the origin in every mode
+        if (lane == 0) ef_store_end<kCodes>(results, end_state, p.out, 0, 0u, 0u, 0u);
+        return;
+    }
+    extern __shared__ uint8_t ef_drow[];  // [groups][G + ld_max + G] db bytes
+    uint8_t *myrow = ef_drow + (size_t)grp * (ld_max + 2 * G) + G;
+    for (uint32_t i = (uint32_t)lane; i < ld; i += G) {
+        if constexpr (kSub)
+            myrow[i] = (uint8_t)ef_sub_code(ef_sub, d[i]);
+        else
+            myrow[i] = d[i];
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    __builtin_amdgcn_wave_barrier();
+
+    const int32_t o = sc.open, e = sc.extend;
+    const uint32_t col0 = (uint32_t)lane * K;  // my columns: col0+1 .. col0+K
+    const uint32_t jend = lq - 1;
+    const uint32_t l_end = jend / K, k_end = jend % K;  // the lane and register of column lq
+    uint32_t qc[K];
+    int32_t Hp[K], Dn[K];
+    int32_t hd = ef_row0<K, kMode, kSub, true>(qs + p.q_off, lq, col0, o, e, qc, Hp, Dn, ef_sub, xdrop);
+    // column 0, entering lane 0: the deletion run P(r, 0) = o + r e, r = t + 1
+    // the row of lane 0 at step t, pruned once it lies below -X (bHx below);
+    // I(r, 1) is -inf
+    const int32_t bF = kEfNeg;
+    int32_t pubF = kEfNeg, pubH = kEfNeg;
+    EfBest best = ef_best_row0<kMode>(lq, o, e);
+    uint8_t *crow = nullptr;
+    if constexpr (kCodes) crow = codes + p.code_off + (size_t)lane * (K / 2);
+    EfDrop<K> xd;
+#pragma unroll
+    for (int k = 0; k < K; ++k) xd.Bp[k] = col0 + (uint32_t)k + 1 <= lq ? 0 : kEfPadB;
+    xd.pubB = 0;
+    xd.X = xdrop;
+    const bool real = col0 < lq;  // I hold a real column
+    const int T = (int)ld + G - 1;
+    uint32_t steps = (uint32_t)T;
+    for (int t = 0; t < T; ++t) {
+        const int r = t - lane + 1;
+        const uint32_t dch = myrow[t - lane];  // d[r-1]; the pads cover rows outside the db
+        const int32_t inF = ef_shr1<G>(bF, pubF);  // I(r, col0+1)
+        const int32_t c0 = o + (t + 1) * e;
+        const int32_t bHx = c0 < -xdrop ? kEfNeg : c0;
+        xd.inB = ef_shr1<G>(0, xd.pubB);            // B(r, col0)
+        const int32_t inH = ef_shr1<G>(bHx, pubH);  // P(r, col0)
+        bool alive = r < 1;
+        if (r >= 1 && r <= (int)ld) {
+            EfCodes<K> row;
+            ef_row<K, kMode, kCodes, kSub, true>(qc, dch, inF, inH, sc, k_end, (uint32_t)r, Hp, Dn, hd, pubF, pubH,
+                                                 best, row, ef_sub, &xd);
+            if constexpr (kCodes) {
+                // lanes wholly past the query store nothing
+                if (col0 < lq) ef_store_codes<K>(crow + (size_t)(r - 1) * p.row_bytes, row);
+            }
+            alive = xd.alive || hd != kEfNeg;  // hd: P(r, col0)
+        }
+        if (!ef_group_any<G>(alive && real)) {
+            steps = (uint32_t)t + 1;
+            break;
+        }
+    }
+    ef_reduce_best<G, kMode, kCodes>(lane, (uint32_t)lane == l_end, best.v, best.i, col0 + best.k + 1, best.k, lq,
+                                     results, end_state, p.out, steps);
 }
 
 // One pair per lane.  Words are written back to front so that they end at
@@ -227,6 +340,7 @@ struct FillLaunch {
     EfScoring sc;
     uint32_t ld_max;
     const uint8_t *sub;
+    int32_t xdrop;  // kEfNoXdrop: the plain fills
 };
 
 template <int G, int K>
@@ -236,6 +350,19 @@ hipError_t fill_class(const FillLaunch &a) {
                            a.codes, a.end_state, a.results, a.sc, a.ld_max, a.sub);
         return hipGetLastError();
     };
+    if (a.xdrop != kEfNoXdrop) {  // extension only: the host has checked mode and X
+        auto gox = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, a.grid, a.block, a.lds, a.s, a.pairs, a.first, a.count, a.qs, a.ds,
+                               a.codes, a.end_state, a.results, a.sc, a.ld_max, a.sub, a.xdrop);
+            return hipGetLastError();
+        };
+        if (a.mode != SALN_MODE_EXTEND || a.xdrop < 0) return hipErrorInvalidValue;
+        return ef_with_flag(a.sub != nullptr, [&](auto sb) {
+            constexpr bool kSub = decltype(sb)::value;
+            return a.codes ? gox(ef_xdrop_fill_kernel<G, K, true, kSub>)
+                           : gox(ef_xdrop_fill_kernel<G, K, false, kSub>);
+        });
+    }
     return ef_with_mode(a.mode, [&](auto m) {
         return ef_with_flag(a.sub != nullptr, [&](auto sb) {
             constexpr int kMode = decltype(m)::value;
@@ -251,7 +378,7 @@ hipError_t fill_class(const FillLaunch &a) {
 hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t first, uint32_t count,
                           uint32_t ld_max, const uint8_t *qs, const uint8_t *ds, EfScoring sc,
                           const uint8_t *sub, uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
-                          hipStream_t s) {
+                          hipStream_t s, int32_t xdrop) {
     if (count == 0) return hipSuccess;
     if (cls < 0 || cls >= kEfClasses || ld_max > kEfMaxDb) return hipErrorInvalidValue;
     const uint32_t G = (uint32_t)kEfClass[cls].lanes;
@@ -263,7 +390,7 @@ hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t f
     while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > budget) --groups;
     const size_t lds = (size_t)ef_lds_bytes(cls, groups, ld_max);
     const FillLaunch a{mode, dim3((count + groups - 1) / groups), dim3(groups * G), lds, s, pairs, first, count,
-                       qs, ds, codes, end_state, results, sc, ld_max, sub};
+                       qs, ds, codes, end_state, results, sc, ld_max, sub, xdrop};
     switch (cls) {
         case 0: return fill_class<16, 10>(a);
         case 1: return fill_class<16, 16>(a);

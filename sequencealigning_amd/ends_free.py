@@ -27,6 +27,16 @@ against a db base; the db is the reference sequence).
   (score 0, no words, coordinates 0).  ``extend_align(..., direction="left")``
   extends leftwards from an anchor at the sequences' ends.
 
+``xdrop=X`` (an int >= 0; ``ends_free_align_batch``, ``extend_align`` and
+``EndsFreePlan``, mode EXTEND only) is the X-drop extension
+(``saln_ends_free_xdrop_*``): a cell whose value lies more than X below the
+best unpruned value above and left of it is pruned, so the alignment cannot
+cross a stretch that costs more than X, and the fill leaves a pair once
+nothing unpruned is left on its front.  The result depends only on the pair,
+the scoring and X; a very large X gives plain extension's.  The records'
+``reserved`` then holds the fill's row-loop steps (``xdrop_steps``).  The
+``*_long`` functions have no ``xdrop``.
+
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
 include/saln.h and DESIGN.md; the checker of the four modes under both kinds
 of scoring is tests/ends_free_model.py.
@@ -201,6 +211,27 @@ def _scoring_entry(entry: str, scoring):
     return entry, _lib.scoring_arg(scoring)
 
 
+def _xdrop_entry(entry: str, mode, xdrop):
+    """(entry point, the arguments between the pair count and the scoring, those
+    after it): `entry` with its mode, or with xdrop (an int: EXTEND only) its
+    saln_ends_free_xdrop_* form, which takes no mode and X after the scoring."""
+    if xdrop is None:
+        return entry, (_mode(mode),), ()
+    if _mode(mode) != EXTEND:
+        raise ValueError("xdrop is part of extension alignment: mode must be EXTEND")
+    if isinstance(xdrop, bool) or int(xdrop) != xdrop:
+        raise ValueError(f"xdrop {xdrop!r} is not an integer")
+    return entry.replace("saln_ends_free_", "saln_ends_free_xdrop_", 1), (), (int(xdrop),)
+
+
+def xdrop_steps(results):
+    """The row-loop steps each pair's group of lanes ran under ``xdrop=`` (the
+    records' ``reserved``; 0 without xdrop): a diagnostic that, unlike the rest
+    of a record, depends on the class geometry.  At most min(m, L) + lanes,
+    L the last db row with an unpruned cell; a plain fill runs m + lanes - 1."""
+    return results["reserved"]
+
+
 def _mode(mode) -> int:
     if isinstance(mode, Mode):
         return {Mode.Global: 0, Mode.Local: 1, Mode.SemiGlobal: 2}[mode]
@@ -214,8 +245,9 @@ def _pair_lists(pairs, n_q, n_db):
     return np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1]), len(pairs)
 
 
-def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar, device):
+def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar, device, xdrop=None):
     """saln_ends_free_align_batch or saln_ends_free_long_align_batch (entry)."""
+    entry, mode_arg, x_arg = _xdrop_entry(entry, mode, xdrop)
     qs, qo = pack_csr(queries)
     ds, do = pack_csr(dbs)
     pq, pd, n = _pair_lists(pairs, len(qo) - 1, len(do) - 1)
@@ -225,7 +257,7 @@ def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar,
     entry, sarg = _scoring_entry(entry, scoring)
     _lib.check(getattr(L, entry)(
         _lib.context(device), vp(qs), vp(qo), len(qo) - 1, vp(ds), vp(do), len(do) - 1, vp(pq),
-        vp(pd), n, _mode(mode), sarg, int(trace_budget), int(bool(cigar)),
+        vp(pd), n, *mode_arg, sarg, *x_arg, int(trace_budget), int(bool(cigar)),
         C.byref(h)), entry)
     try:
         res = np.zeros(n, dtype=_lib.ENDS_FREE_RESULT_DTYPE)
@@ -250,7 +282,7 @@ def _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar,
 
 
 def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace_budget: int = 0,
-                          cigar: bool = True, device: int = 0):
+                          cigar: bool = True, device: int = 0, xdrop=None):
     """Local, semi-global, overlap (mode=OVERLAP) or extension (mode=EXTEND)
     alignment of a batch.
     pairs: None (all-vs-all, db
@@ -260,9 +292,11 @@ def ends_free_align_batch(queries, dbs, pairs=None, *, mode, scoring=None, trace
     CigarBatch (pair k's [(length, op), ...]).  cigar=False runs the fill only:
     score and ends, begins -1, no words.  A pair whose trace codes alone exceed
     trace_budget bytes (0 selects 1 GiB per chunk) has status TRACE_CAP, its
-    score and ends, begins -1 and no words."""
+    score and ends, begins -1 and no words.  xdrop: None, or X >= 0 with
+    mode=EXTEND (ValueError under another mode): the X-drop extension, whose
+    records carry the fill's steps in ``reserved``."""
     return _align_batch("saln_ends_free_align_batch", queries, dbs, pairs, mode, scoring,
-                        trace_budget, cigar, device)
+                        trace_budget, cigar, device, xdrop)
 
 
 def ends_free_align_long_batch(queries, dbs, pairs=None, *, mode, scoring=None,
@@ -321,7 +355,7 @@ def _extend(seq1, seq2, direction, scoring, trace_budget, device, **kw):
 
 
 def extend_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
-                 direction: str = "right"):
+                 direction: str = "right", xdrop=None):
     """(result record, cigar) of the best extension of seq1 (query) and seq2
     (db) from an anchor: the alignment of a prefix seq1[:q_end] with a prefix
     seq2[:db_end] that scores highest, q_begin = db_begin = 0; score 0 and no
@@ -336,8 +370,12 @@ def extend_align(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int
     db_end', db_end = len(seq2); the alignment is seq1[q_begin:] against
     seq2[db_begin:], and the empty one has q_begin = q_end = len(seq1).  A
     SubstitutionMatrix is not transposed by it: its rows stay the db's
-    symbols.  alignment_score takes the result of either direction."""
-    return _extend(seq1, seq2, direction, scoring, trace_budget, device)
+    symbols.  alignment_score takes the result of either direction.
+
+    xdrop=X: the X-drop extension (the module's text), in either direction;
+    leftwards the drop-off is counted from the anchor at the right ends."""
+    kw = {} if xdrop is None else {"xdrop": xdrop}
+    return _extend(seq1, seq2, direction, scoring, trace_budget, device, **kw)
 
 
 def extend_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
@@ -485,9 +523,11 @@ class EndsFreePlan:
     list once, execute on device (torch) sequence buffers into a device tensor
     of result records (n_pairs x 8 int32: score, status, q_begin = -1, q_end,
     db_begin = -1, db_end, 0, 0).  scoring: the 4-tuple or a SubstitutionMatrix
-    (saln_ends_free_sub_plan_create: the database-search shape)."""
+    (saln_ends_free_sub_plan_create: the database-search shape).  xdrop: None,
+    or X >= 0 with mode=EXTEND: the X-drop extension
+    (saln_ends_free_xdrop_plan_create), the last int32 then the fill's steps."""
 
-    def __init__(self, q_off, db_off, pairs=None, *, mode, scoring=None, device: int = 0):
+    def __init__(self, q_off, db_off, pairs=None, *, mode, scoring=None, device: int = 0, xdrop=None):
         L = _lib.lib()
         self._L = L
         self.device = device
@@ -497,9 +537,10 @@ class EndsFreePlan:
         self.n_pairs = n
         vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
         self._h = C.c_void_p()
-        entry, sarg = _scoring_entry("saln_ends_free_plan_create", scoring)
+        entry, mode_arg, x_arg = _xdrop_entry("saln_ends_free_plan_create", mode, xdrop)
+        entry, sarg = _scoring_entry(entry, scoring)
         _lib.check(getattr(L, entry)(_lib.context(device), vp(qo), len(qo) - 1, vp(do), len(do) - 1,
-                                     vp(pq), vp(pd), n, _mode(mode), sarg, C.byref(self._h)), entry)
+                                     vp(pq), vp(pd), n, *mode_arg, sarg, *x_arg, C.byref(self._h)), entry)
 
     def execute(self, d_q, d_db, d_results, stream=None):
         """d_q / d_db: device uint8 tensors (CSR bytes), d_results: device

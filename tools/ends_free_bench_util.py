@@ -1,5 +1,5 @@
 """What the ends-free bench tools share (bench_ends_free.py, _long, _replay,
-_sub, bench_overlap.py, bench_extend.py): the two timers, the two pair
+_sub, bench_overlap.py, bench_extend.py, bench_xdrop.py): the two timers, the two pair
 generators, the raw C batch call and the sample check against the plain model
 tests/ends_free_model.py.  Importing it puts the repository and tests/ on the
 path."""
