@@ -1607,6 +1607,48 @@ struct RowIn {
     uint32_t w;
 };
 
+// The packed fill's sequence reads (fill_pk_body's prologue): whole aligned
+// dwords, all issued before the first wait.  seq_words_issue loads the N + 1
+// aligned dwords from the one that holds byte s[o] (o >= 0) on, each address
+// clamped to the last aligned dword that holds a byte of the n >= 1 bytes at
+// s; seq_words shifts them to the N words of bytes s[o .. o + 4 N).  The first
+// address is at or above s's own dword (o >= 0) and none is above the dword
+// of s[n - 1], so every dword read holds a byte of the sequence itself: no
+// read touches a page the sequence does not (an aligned dword never crosses a
+// page), whatever the sequence's offset in its buffer and wherever the
+// buffer ends - the argument of the walker's 16-byte query chunks
+// (nw_traceback_lds_kernel).  A clamped dword stands for bytes past s[n - 1]
+// only; the callers mask those (seq_pad).
+template <int N>
+__device__ __forceinline__ void seq_words_issue(const uint8_t *__restrict__ s, uint32_t n, int32_t o,
+                                                uint32_t (&raw)[N + 1]) {
+    // (offsets from s, not addresses: the loads stay global loads)
+    const int32_t al = (int32_t)((uintptr_t)s & 3u);
+    const int32_t first = ((al + o) & ~3) - al, last = ((al + (int32_t)n - 1) & ~3) - al;
+#pragma unroll
+    for (int i = 0; i <= N; ++i) {
+        const int32_t a = first + 4 * i;
+        raw[i] = *reinterpret_cast<const uint32_t *>(s + (a < last ? a : last));
+    }
+}
+template <int N>
+__device__ __forceinline__ void seq_words(const uint8_t *s, int32_t o, const uint32_t (&raw)[N + 1],
+                                          uint32_t (&w)[N]) {
+    const uint32_t sh = (uint32_t)((uintptr_t)s + (uint32_t)o) & 3u;
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], sh);
+}
+// w with its bytes from the nv-th on (nv may lie outside [0, 4]) replaced by pad's
+__device__ __forceinline__ uint32_t seq_pad(uint32_t w, int32_t nv, uint32_t pad) {
+    const uint32_t keep = nv >= 4 ? ~0u : nv <= 0 ? 0u : (1u << (8 * (nv & 3))) - 1u;
+    return bfi(keep, w, pad);
+}
+// non-zero exactly when a byte of w is not one of A, C, G, T (acgt() on words)
+__device__ __forceinline__ uint32_t not_acgt4(uint32_t w) {
+    constexpr uint32_t kAcgt = 'A' | 'C' << 8 | 'T' << 16 | 'G' << 24;
+    return __builtin_amdgcn_perm(0u, kAcgt, (w >> 1) & 0x03030303u) ^ w;
+}
+
 // Returns (per lane; wave-uniform over the lanes that hold pairs): 0 filled
 // (or no pair), 1 the table body left the wave's pairs to the fallback launch
 // (a byte other than A, C, G, T), 2 the fallback body found nothing to do.
@@ -1670,9 +1712,9 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
     const uint32_t ia = 2 * gi, ib = 2 * gi + 1;
     if (ia >= count) return 0;  // whole group
     const bool hasB = ib < count;
+    // both descriptors in one round trip (a group without a B pair reads A's twice)
     const NwPairDesc pa = src.pair(ia);
-    NwPairDesc pb = pa;
-    if (hasB) pb = src.pair(ib);
+    const NwPairDesc pb = src.pair(hasB ? ib : ia);
     const int ldA = (int)pa.len_db, ldB = hasB ? (int)pb.len_db : 0;
     const int lqA = (int)pa.len_q, lqB = hasB ? (int)pb.len_q : 0;
     const uint8_t *__restrict__ qA = qs + pa.q_off;
@@ -1693,7 +1735,6 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
     const uint32_t kProfBase = cmm * 0x01010101u, kProfStep = cm - cmm;  // kRowProf
     const uint32_t kCmm2 = cmm * 0x00010001u;  // full codes' eq sign in the free frame
     constexpr uint32_t kAcgt = 'A' | 'C' << 8 | 'T' << 16 | 'G' << 24;
-    auto acgt = [](uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; };
     bool bad = false;  // kTabMode: a byte other than A, C, G, T in this lane's share
     const uint32_t kRebaseAdd = cst2(-drift * kRebaseSteps);
     const int32_t ctr = kRebase ? rebase_center(sc, G * K) : 0;  // frame centring (kRebase)
@@ -1704,31 +1745,102 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
     // does not split it into halves
     uint32_t qc[K], Hp[K], Dn[K];
     const uint32_t pen1 = 2 * (sc.match - sc.mismatch);  // kProf: the mismatch byte
+    uint32_t *__restrict__ myrow = drow + (threadIdx.x / G) * (ld_max + 2 * G) + G;
+    uint16_t *__restrict__ myrow16 = reinterpret_cast<uint16_t *>(drow) +
+                                     (threadIdx.x / G) * (ld_max + 2 * G) + G;
+    // Every sequence read of the start-up is issued here, before the first
+    // wait: the aligned dwords that cover this lane's K query bytes of both
+    // pairs (kProf: one query), and the first kDbB row quads of its share of
+    // the db rows (lane `lane` stages rows 4m .. 4m + 3 of the quads
+    // m = lane + G u).  (seq_words_issue: which dwords, and why they are safe.)
+    constexpr int NQ = (K + 3) / 4;
+    constexpr int kDbB = G >= 32 ? 2 : G >= 16 ? 3 : 5;  // >= 152 rows per batch
+    constexpr uint32_t kA4 = 0x41414141u;
+    uint32_t qrA[NQ + 1], qrB[NQ + 1], dr[kDbB][2][2];
+    seq_words_issue<NQ>(qA, pa.len_q, col0, qrA);
+    if constexpr (!kProf) seq_words_issue<NQ>(qB, pb.len_q, col0, qrB);
+    auto db_issue = [&](int m0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < kDbB; ++u) {
+            const int32_t o = 4 * (m0 + lane + G * u);
+            seq_words_issue<1>(dA, pa.len_db, o, dr[u][0]);
+            seq_words_issue<1>(dB, pb.len_db, o, dr[u][1]);
+        }
+    };
+    // rows past a pair's last: char 0, as the fill always staged them; the
+    // words past row ldM - 1 (at most three, inside the G pad words) are
+    // read only by steps whose body is skipped
+    auto db_store = [&](int m0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < kDbB; ++u) {
+            const int i0 = 4 * (m0 + lane + G * u);
+            if (i0 >= ldM) continue;
+            uint32_t wa[1], wb[1];
+            seq_words<1>(dA, i0, dr[u][0], wa);
+            seq_words<1>(dB, i0, dr[u][1], wb);
+            if constexpr (kTab || kTabMode == 2)
+                bad |= (not_acgt4(seq_pad(wa[0], ldA - i0, kA4)) |
+                        not_acgt4(seq_pad(wb[0], ldB - i0, kA4))) != 0;
+            uint32_t a = seq_pad(wa[0], ldA - i0, 0u), b = seq_pad(wb[0], ldB - i0, 0u);
+            if constexpr (kTab) {
+                a = (a >> 1) & 0x03030303u;
+                b = (b >> 1) & 0x03030303u;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if constexpr (kRebase) {
+                    myrow16[i0 + c] = (uint16_t)__builtin_amdgcn_perm(b, a, 0x0C0C0400u + 0x0101u * c);
+                } else {
+                    // [A, 0, B, 0]
+                    const uint32_t x = __builtin_amdgcn_perm(b, a, 0x0C040C00u + 0x00010001u * c);
+                    myrow[i0 + c] = kRowProf ? (x << 3 | 0x60006000u) : kTab ? (x | 0x0C000C00u) : x << 5;
+                }
+            }
+        }
+    };
+    db_issue(0);
+    {
+        uint32_t wA[NQ], wB[NQ];
+        seq_words<NQ>(qA, col0, qrA, wA);
+        if constexpr (!kProf) seq_words<NQ>(qB, col0, qrB, wB);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int32_t nvA = lqA - col0 - 4 * i, nvB = lqB - col0 - 4 * i;
+            if constexpr (kTab || kTabMode == 2)
+                bad |= (not_acgt4(seq_pad(wA[i], nvA, kA4)) | not_acgt4(seq_pad(wB[i], nvB, kA4))) != 0;
+            wA[i] = seq_pad(wA[i], nvA, 0u);
+            if constexpr (!kProf) wB[i] = seq_pad(wB[i], nvB, 0u);
+            if constexpr (kTab) {  // codes; a padding byte's is 0, as 'A''s
+                wA[i] = (wA[i] >> 1) & 0x03030303u;
+                wB[i] = ((wB[i] >> 1) & 0x03030303u) + (kRowProf ? 0x04040404u : 0u);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int j = col0 + k + 1;
+            const uint32_t qch = __builtin_amdgcn_ubfe(wA[k / 4], 8 * (k % 4), 8);
+            if constexpr (kProf && kFree) {  // bonus against A, C, T, G; padding: all mismatch
+                qc[k] = (qch == 'A' ? cm : cmm) | (qch == 'C' ? cm : cmm) << 8 |
+                        (qch == 'T' ? cm : cmm) << 16 | (qch == 'G' ? cm : cmm) << 24;
+            } else if constexpr (kProf) {  // penalty against A, C, T, G (codes 0-3); padding: all mismatch
+                qc[k] = (qch == 'A' ? 0u : pen1) | (qch == 'C' ? 0u : pen1 << 8) |
+                        (qch == 'T' ? 0u : pen1 << 16) | (qch == 'G' ? 0u : pen1 << 24);
+            } else if constexpr (kTab) {
+                // codes in bytes 0 / 2 (padding: code 0).  kRowProf: the v_perm
+                // selector of the row profiles (A: bytes 0-3 of the lo dword,
+                // B: bytes 4-7 = the hi dword; 0x0C = zero byte)
+                const uint32_t x = __builtin_amdgcn_perm(wB[k / 4], wA[k / 4],
+                                                         0x0C040C00u + 0x00010001u * (k % 4));
+                qc[k] = kRowProf ? (x | 0x0C000C00u) : x;
+            } else {
+                const uint32_t cb = __builtin_amdgcn_ubfe(wB[k / 4], 8 * (k % 4), 8);
+                qc[k] = (j <= lqA ? qch << 5 : 0xE000u) | (j <= lqB ? cb << 5 : 0xE000u) << 16;
+            }
+        }
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int j = col0 + k + 1;
-        if constexpr (kProf && kFree) {  // bonus against A, C, T, G; padding: all mismatch
-            const uint32_t qch = j <= lqA ? (uint32_t)qA[j - 1] : 0u;
-            qc[k] = (qch == 'A' ? cm : cmm) | (qch == 'C' ? cm : cmm) << 8 |
-                    (qch == 'T' ? cm : cmm) << 16 | (qch == 'G' ? cm : cmm) << 24;
-        } else if constexpr (kProf) {  // penalty against A, C, T, G (codes 0-3); padding: all mismatch
-            const uint32_t qch = j <= lqA ? (uint32_t)qA[j - 1] : 0u;
-            qc[k] = (qch == 'A' ? 0u : pen1) | (qch == 'C' ? 0u : pen1 << 8) |
-                    (qch == 'T' ? 0u : pen1 << 16) | (qch == 'G' ? 0u : pen1 << 24);
-        } else if constexpr (kTab) {  // codes in bytes 0 / 2 (padding: code 0)
-            const uint32_t ca = j <= lqA ? (uint32_t)qA[j - 1] : 'A';
-            const uint32_t cb = j <= lqB ? (uint32_t)qB[j - 1] : 'A';
-            bad |= !acgt(ca) || !acgt(cb);
-            // kRowProf: the v_perm selector of the row profiles (A: bytes 0-3
-            // of the lo dword, B: bytes 4-7 = the hi dword; 0x0C = zero byte)
-            qc[k] = kRowProf ? (((ca >> 1) & 3u) | 0x0C00u | (((cb >> 1) & 3u) + 4u) << 16 | 0x0C000000u)
-                             : (((ca >> 1) & 3u) | ((cb >> 1) & 3u) << 16);
-        } else {
-            const uint32_t ca = j <= lqA ? (uint32_t)qA[j - 1] << 5 : 0xE000u;
-            const uint32_t cb = j <= lqB ? (uint32_t)qB[j - 1] << 5 : 0xE000u;
-            if constexpr (kTabMode == 2) bad |= (j <= lqA && !acgt(ca >> 5)) || (j <= lqB && !acgt(cb >> 5));
-            qc[k] = ca | (cb << 16);
-        }
         const int32_t h0 = up(hs_row0(sc, (uint32_t)j)) + beta * j - ctr;     // H~(0, j)
         const int32_t d1 = up(ds_row1(sc, (uint32_t)j)) + alpha + beta * j - ctr;  // D~(1, j)
         Hp[k] = pkx(h0, h0);
@@ -1745,25 +1857,12 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
     // a clamp (the pad words are only read by steps whose body is skipped).
     // kRebase (long db): the row's two chars as a 16-bit (A | B << 8) word,
     // half the LDS, widened in the step (one v_perm and a shift)
-    uint32_t *__restrict__ myrow = drow + (threadIdx.x / G) * (ld_max + 2 * G) + G;
-    uint16_t *__restrict__ myrow16 = reinterpret_cast<uint16_t *>(drow) +
-                                     (threadIdx.x / G) * (ld_max + 2 * G) + G;
-    for (int i = lane; i < ldM; i += G) {
-        const uint32_t ca = i < ldA ? (uint32_t)dA[i] : 0u;
-        const uint32_t cb = i < ldB ? (uint32_t)dB[i] : 0u;
-        if constexpr (kRebase) {
-            if constexpr (kTabMode == 2) bad |= (i < ldA && !acgt(ca)) || (i < ldB && !acgt(cb));
-            myrow16[i] = (uint16_t)(ca | (cb << 8));
-        } else if constexpr (kRowProf) {
-            bad |= (i < ldA && !acgt(ca)) || (i < ldB && !acgt(cb));
-            myrow[i] = ((ca >> 1) & 3u) << 3 | ((cb >> 1) & 3u) << 19 | 0x60006000u;
-        } else if constexpr (kTab) {
-            bad |= (i < ldA && !acgt(ca)) || (i < ldB && !acgt(cb));
-            myrow[i] = ((ca >> 1) & 3u) | ((cb >> 1) & 3u) << 16 | 0x0C000C00u;
-        } else {
-            if constexpr (kTabMode == 2) bad |= (i < ldA && !acgt(ca)) || (i < ldB && !acgt(cb));
-            myrow[i] = (ca << 5) | (cb << 21);
-        }
+    // (the first batch's loads were issued with the query's; a longer db
+    // takes a round trip per further batch)
+    db_store(0);
+    for (int m0 = G * kDbB; 4 * m0 < ldM; m0 += G * kDbB) {
+        db_issue(m0);
+        db_store(m0);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
     __builtin_amdgcn_wave_barrier();
@@ -2103,6 +2202,16 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
             step(t + 1, HpB, Hp, S1, d1);
         }
     }
+    // The table fill's last steps (the ramp down: lanes go idle one by one)
+    // issue below a pipelined walk's later pairs (priority 1,
+    // nw_traceback_lds_kernel).  With the start-up's loads batched the fill
+    // no longer leaves the walk the issue slots of ~80 serial round trips per
+    // wave, and the walk outlasted it (step 0.832-0.834 -> 0.854-0.860 ms);
+    // yielding here gives part of them back: 0.834-0.837 against 0.843-0.846
+    // (profiles/fill_prologue_ab.jsonl).  Lowering it
+    // in the first steps instead, or for more than these, was slower than
+    // either.
+    if constexpr (kTab) __builtin_amdgcn_s_setprio(0);
     for (; t + 1 < T; t += 2) {
         step(t, Hp, HpB, G0, z);
         step(t + 1, HpB, Hp, G0, z);
