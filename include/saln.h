@@ -902,8 +902,9 @@ int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols
  * fill runs m + G - 1 steps.
  * The entry points are their plain counterparts without `mode` and with
  * xdrop; saln_ends_free_execute / _plan_destroy and saln_ends_free_aln_count /
- * _get / _free serve them unchanged.  The chunked fill and the tiled replay
- * have no X-drop form. */
+ * _get / _free serve them unchanged.  Pairs above the limits:
+ * saln_ends_free_xdrop_long_align_batch, below.  The tiled replay has no X-drop
+ * form. */
 int saln_ends_free_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
                                      uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
                                      uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
@@ -915,6 +916,37 @@ int saln_ends_free_xdrop_plan_create(saln_context *ctx, const uint64_t *q_off, u
                                      const uint32_t *pair_db, uint64_t n_pairs,
                                      const saln_nw_scoring *scoring, int32_t xdrop,
                                      saln_ends_free_plan **out);
+
+/* X-drop extension of pairs of any length (ends_free_xdrop_long_kernels.hip).
+ * saln_ends_free_xdrop_long_align_batch is saln_ends_free_long_align_batch
+ * (below) without `mode` and with xdrop: the definition above, the long entry
+ * point's arguments, code sizes (saln_ends_free_long_trace_bytes: all m rows),
+ * trace budget, chunking and SALN_TRACE_CAP.  The only limit is the range
+ * guard, (n + m + 2) * max|parameter| + xdrop < 2^30; a negative xdrop, a pair
+ * outside the guard and a NULL matrix are SALN_E_INVALID with a message, before
+ * the device is touched.  Records (all fields but `reserved`) and words depend
+ * on the pair, the scoring and X alone: they are the class form's for every
+ * pair both can run.
+ *  - A pair within the class limits (saln_ends_free_long_pair_path: long_fill
+ *    0) runs saln_ends_free_xdrop_align_batch's fill and reports its steps.
+ *  - Every other pair runs the chunked X-drop fill: chunks of 1,024 query
+ *    columns, left to right.  A chunk runs only the rows from its first to its
+ *    last row that can hold an unpruned cell (from row 1 where row 0 is
+ *    unpruned at its left edge, else from the first row whose cell in the
+ *    column left of it is unpruned; at least down to the last row the chunk
+ *    before ran), and the pair ends at the first chunk that nothing unpruned
+ *    enters.  Codes of rows and chunks that did not run are not written; the
+ *    walk never reads them.
+ *  - `reserved`: the row-loop steps summed over the chunks the pair ran,
+ *    saturating at 2^32 - 1: per chunk at most (its rows) + 63 + 1.
+ *  - Workspace: per wave one boundary column of 16 bytes per db row (P, I and
+ *    B of the next chunk's first column), at most 256 MiB per launch. */
+int saln_ends_free_xdrop_long_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                          uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                          uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                          uint64_t n_pairs, const saln_nw_scoring *scoring, int32_t xdrop,
+                                          uint64_t trace_budget_bytes, int want_cigar,
+                                          saln_ends_free_aln **out);
 
 /* Pairs of any length (ends_free_long_kernels.hip, ends_free_long_host.cpp).
  * saln_ends_free_long_align_batch is saln_ends_free_align_batch without the
@@ -1069,6 +1101,14 @@ int saln_ends_free_sub_xdrop_plan_create(saln_context *ctx, const uint64_t *q_of
                                          const uint32_t *pair_db, uint64_t n_pairs,
                                          const saln_sub_matrix *matrix, int32_t xdrop,
                                          saln_ends_free_plan **out);
+/* saln_ends_free_xdrop_long_align_batch (above) under a matrix. */
+int saln_ends_free_sub_xdrop_long_align_batch(saln_context *ctx, const uint8_t *q_seq,
+                                              const uint64_t *q_off, uint64_t n_q, const uint8_t *db_seq,
+                                              const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                              const uint32_t *pair_db, uint64_t n_pairs,
+                                              const saln_sub_matrix *matrix, int32_t xdrop,
+                                              uint64_t trace_budget_bytes, int want_cigar,
+                                              saln_ends_free_aln **out);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

@@ -18,7 +18,8 @@ from .wfa_affine import wfa_affine_align, wfa_affine_align_batch
 from . import ends_free
 from .ends_free import (EndsFreePlan, SubstitutionMatrix, alignment_score, ends_free_align_batch,
                         ends_free_align_long_batch, extend_align, extend_align_long, local_align, local_align_long, overlap_align,
-                        overlap_align_long, semi_global_align, semi_global_align_long, xdrop_steps)
+                        overlap_align_long, semi_global_align, semi_global_align_long, xdrop_extend_long, xdrop_extend_long_batch,
+                        xdrop_steps)
 from ._lib import get_option, option_names, options, set_option
 
 __all__ = [
@@ -30,5 +31,6 @@ __all__ = [
     "ends_free", "EndsFreePlan", "SubstitutionMatrix", "alignment_score", "ends_free_align_batch", "local_align", "semi_global_align",
     "ends_free_align_long_batch", "local_align_long", "semi_global_align_long",
     "overlap_align", "overlap_align_long", "extend_align", "extend_align_long", "xdrop_steps",
+    "xdrop_extend_long_batch", "xdrop_extend_long",
     "get_option", "option_names", "options", "set_option",
 ]

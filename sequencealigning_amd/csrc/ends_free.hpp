@@ -136,6 +136,15 @@ inline uint32_t ef_long_slots(uint64_t count, uint64_t ld_max) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({count, kEfLongWaves, fit}));
 }
 
+// The same for the chunked X-drop fill (ends_free_xdrop_long_kernels.hip,
+// saln_ends_free_xdrop_long_*): an entry also holds B, 16 bytes per row, so
+// half as many slots fit the same kEfLongWorkspace.
+constexpr uint32_t kEfXdropBndBytes = 16;
+inline uint32_t ef_xdrop_long_slots(uint64_t count, uint64_t ld_max) {
+    const uint64_t fit = kEfLongWorkspace / (kEfXdropBndBytes * (ld_max ? ld_max : 1));
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({count, kEfLongWaves, fit}));
+}
+
 // Tiled replay traceback (ends_free_replay_kernels.hip, saln_ends_free_replay_*,
 // DESIGN.md section 3e): what a pair of the chunked path keeps in place of its
 // codes, from the pair's code_off on.  R: rows of a tile (a power of two).
@@ -202,6 +211,15 @@ hipError_t launch_ef_fill_long(int32_t mode, const EfPair *pairs, uint32_t first
                                const uint8_t *qs, const uint8_t *ds, EfScoring sc, const uint8_t *sub,
                                uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results, void *bnd,
                                uint64_t slot_rows, uint32_t slots, uint32_t *counter, hipStream_t s);
+// Chunked X-drop extension fill (SALN_MODE_EXTEND, xdrop = X >= 0) of
+// pairs[first .. first + count): as launch_ef_fill_long, with slot_rows entries
+// of kEfXdropBndBytes per slot; leaves the pairs' row-loop steps, summed over
+// the chunks they ran, in the records' `reserved`.
+hipError_t launch_ef_xdrop_fill_long(const EfPair *pairs, uint32_t first, uint32_t count, const uint8_t *qs,
+                                     const uint8_t *ds, EfScoring sc, const uint8_t *sub, int32_t xdrop,
+                                     uint8_t *codes, uint8_t *end_state, saln_ends_free_result *results,
+                                     void *bnd, uint64_t slot_rows, uint32_t slots, uint32_t *counter,
+                                     hipStream_t s);
 // The forward pass of the tiled replay: the chunked fill, score only, of
 // pairs[first .. first + count), keeping each pair's boundary columns and
 // checkpoint rows at area + code_off (ef_replay_layout with tile_rows) and its

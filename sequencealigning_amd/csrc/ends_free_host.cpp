@@ -112,15 +112,16 @@ int make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::
     return SALN_OK;
 }
 
-// An X-drop call's X (kEfNoXdrop: none): >= 0, extension only, the class fills only.
-int check_xdrop(int32_t xdrop, int32_t mode, bool long_ok) {
+// An X-drop call's X (kEfNoXdrop: none): >= 0, extension only, and not under
+// the tiled replay (the class fills and the chunked fill have X-drop forms).
+int check_xdrop(int32_t xdrop, int32_t mode, bool replay) {
     if (xdrop == kEfNoXdrop) return SALN_OK;
     if (xdrop < 0) {
         set_error("ends_free: xdrop " + std::to_string(xdrop) + " is negative (X >= 0)");
         return SALN_E_INVALID;
     }
-    if (mode != SALN_MODE_EXTEND || long_ok) {
-        set_error("ends_free: X-drop is part of SALN_MODE_EXTEND under the class fills only");
+    if (mode != SALN_MODE_EXTEND || replay) {
+        set_error("ends_free: X-drop is part of SALN_MODE_EXTEND, and the tiled replay has no X-drop form");
         return SALN_E_INVALID;
     }
     return SALN_OK;
@@ -190,16 +191,19 @@ int build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uin
 
 // The fills of `pairs` (device copy d_pairs, in plan_launches' order).  ws:
 // the chunked fill's workspace (launches of kEfLongClass need one).  xdrop:
-// kEfNoXdrop or the class fills' X (check_xdrop: no launch is chunked then).
+// kEfNoXdrop or X: every launch then runs its fill's X-drop form.
 int run_fills(const std::vector<Launch> &launches, int32_t mode, const EfPair *d_pairs,
               const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc, const uint8_t *d_sub,
               uint8_t *d_codes, uint8_t *d_end_state, saln_ends_free_result *d_results, hipStream_t s,
               EfLongWorkspace *ws = nullptr, int32_t xdrop = kEfNoXdrop) {
     for (const Launch &l : launches) {
         if (l.cls == kEfLongClass) {
-            if (!ws || xdrop != kEfNoXdrop) return SALN_E_INVALID;
-            const int rc = ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
-                                        d_codes, d_end_state, d_results, s);
+            if (!ws) return SALN_E_INVALID;
+            const int rc = xdrop == kEfNoXdrop
+                               ? ef_long_fill(ws, mode, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
+                                              d_codes, d_end_state, d_results, s)
+                               : ef_xdrop_long_fill(ws, d_pairs, l.first, l.count, l.ld_max, d_q, d_db, sc, d_sub,
+                                                    xdrop, d_codes, d_end_state, d_results, s);
             if (rc != SALN_OK) return rc;
             continue;
         }
@@ -402,7 +406,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     uint64_t max_abs = 0;
     std::vector<uint8_t> block;
     int rc = check_mode(mode);
-    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, long_ok);
+    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, tile_rows != 0);
     if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs, &block);
     std::vector<EfPair> all;
     if (rc == SALN_OK)

@@ -26,7 +26,10 @@ struct EfScoreSrc {
 // saln_ends_free_replay_align_batch (a chunk holds replay footprints, and the
 // alignments of its chunked-path pairs come from ef_replay_run).  xdrop:
 // kEfNoXdrop, or the X of saln_ends_free_xdrop_align_batch (mode
-// SALN_MODE_EXTEND, long_ok false: the class fills' X-drop instances).
+// SALN_MODE_EXTEND, long_ok false: the class fills' X-drop instances) and of
+// saln_ends_free_xdrop_long_align_batch (long_ok true, tile_rows 0: pairs
+// above the limits run the chunked X-drop fill, ef_xdrop_long_fill).  The
+// replay has no X-drop form: tile_rows != 0 with an X is refused.
 // ends_free_host.cpp.
 int ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                    const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
@@ -58,6 +61,14 @@ int ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs, uint3
                  uint32_t count, uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db,
                  const EfScoring &sc, const uint8_t *d_sub, uint8_t *d_codes, uint8_t *d_end_state,
                  saln_ends_free_result *d_results, hipStream_t s);
+
+// The same launch of the chunked X-drop fill (SALN_MODE_EXTEND, xdrop >= 0):
+// ef_xdrop_long_slots waves, whose boundary entries hold 16 bytes per row.
+// ends_free_long_host.cpp.
+int ef_xdrop_long_fill(EfLongWorkspace *ws, const EfPair *d_pairs, uint32_t first, uint32_t count,
+                       uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc,
+                       const uint8_t *d_sub, int32_t xdrop, uint8_t *d_codes, uint8_t *d_end_state,
+                       saln_ends_free_result *d_results, hipStream_t s);
 
 // Device workspace of a batch's replays, all on one stream: the walks' states
 // and the forward pass's pair counter.

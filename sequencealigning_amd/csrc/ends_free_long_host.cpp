@@ -4,8 +4,11 @@
 // (ends_free_long_kernels.hip); the walk, the gather, the trace-budget chunks
 // and the result handle are shared.  This file holds what the long layout
 // adds: its code size, the path decision as the C ABI reports it, and the
-// launches with their bounded boundary workspace (ef_long_slots).
+// launches with their bounded boundary workspace (ef_long_slots), and the
+// X-drop forms of both (saln_ends_free_xdrop_long_*, ef_xdrop_long_slots).
 #include <hip/hip_runtime.h>
+
+#include <climits>
 
 #include "ends_free_host.hpp"
 
@@ -27,6 +30,25 @@ int saln::ef_long_fill(EfLongWorkspace *ws, int32_t mode, const EfPair *d_pairs,
     HIP_TRY(hipMemsetAsync(ws->counter.p, 0, sizeof(uint32_t), s));
     HIP_TRY(launch_ef_fill_long(mode, d_pairs, first, count, d_q, d_db, sc, d_sub, d_codes, d_end_state,
                                 d_results, ws->bnd.p, slot_rows, slots, ws->counter.as<uint32_t>(), s));
+    return SALN_OK;
+}
+
+int saln::ef_xdrop_long_fill(EfLongWorkspace *ws, const EfPair *d_pairs, uint32_t first, uint32_t count,
+                             uint32_t ld_max, const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc,
+                             const uint8_t *d_sub, int32_t xdrop, uint8_t *d_codes, uint8_t *d_end_state,
+                             saln_ends_free_result *d_results, hipStream_t s) {
+    if (count == 0) return SALN_OK;
+    const uint64_t slot_rows = ld_max ? ld_max : 1;
+    const uint32_t slots = ef_xdrop_long_slots(count, ld_max);
+    const size_t bytes = (size_t)slots * slot_rows * kEfXdropBndBytes;
+    if (bytes > ws->bnd_bytes) {  // alloc waits for the stream's earlier fills
+        HIP_TRY(ws->bnd.alloc(bytes));
+        ws->bnd_bytes = bytes;
+    }
+    if (!ws->counter.p) HIP_TRY(ws->counter.alloc(16));
+    HIP_TRY(hipMemsetAsync(ws->counter.p, 0, sizeof(uint32_t), s));
+    HIP_TRY(launch_ef_xdrop_fill_long(d_pairs, first, count, d_q, d_db, sc, d_sub, xdrop, d_codes, d_end_state,
+                                      d_results, ws->bnd.p, slot_rows, slots, ws->counter.as<uint32_t>(), s));
     return SALN_OK;
 }
 
@@ -75,6 +97,31 @@ int saln_ends_free_sub_long_align_batch(saln_context *ctx, const uint8_t *q_seq,
                                         saln_ends_free_aln **out) {
     return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs, mode,
                           EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out, true);
+}
+
+int saln_ends_free_xdrop_long_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                          uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                          uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                          uint64_t n_pairs, const saln_nw_scoring *scoring, int32_t xdrop,
+                                          uint64_t trace_budget_bytes, int want_cigar,
+                                          saln_ends_free_aln **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;  // negative: refused with a message
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs,
+                          SALN_MODE_EXTEND, EfScoreSrc::of(scoring), trace_budget_bytes, want_cigar, out,
+                          true, 0, xdrop);
+}
+
+int saln_ends_free_sub_xdrop_long_align_batch(saln_context *ctx, const uint8_t *q_seq,
+                                              const uint64_t *q_off, uint64_t n_q, const uint8_t *db_seq,
+                                              const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                              const uint32_t *pair_db, uint64_t n_pairs,
+                                              const saln_sub_matrix *matrix, int32_t xdrop,
+                                              uint64_t trace_budget_bytes, int want_cigar,
+                                              saln_ends_free_aln **out) {
+    if (xdrop == kEfNoXdrop) xdrop = INT32_MIN;
+    return ef_align_batch(ctx, q_seq, q_off, n_q, db_seq, db_off, n_db, pair_q, pair_db, n_pairs,
+                          SALN_MODE_EXTEND, EfScoreSrc::of(matrix), trace_budget_bytes, want_cigar, out,
+                          true, 0, xdrop);
 }
 
 }  // extern "C"

@@ -35,7 +35,12 @@ cross a stretch that costs more than X, and the fill leaves a pair once
 nothing unpruned is left on its front.  The result depends only on the pair,
 the scoring and X; a very large X gives plain extension's.  The records'
 ``reserved`` then holds the fill's row-loop steps (``xdrop_steps``).  The
-``*_long`` functions have no ``xdrop``.
+``*_long`` functions take no ``xdrop``; X-drop extension of pairs of any
+length is ``xdrop_extend_long_batch`` / ``xdrop_extend_long``
+(``saln_ends_free_xdrop_long_*``): a pair above the limits runs the chunked
+X-drop fill (ends_free_xdrop_long_kernels.hip), which runs a chunk of 1,024
+query columns only over the rows between its first and last unpruned cell and
+leaves the pair at the first chunk without one.
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
 include/saln.h and DESIGN.md; the checker of the four modes under both kinds
@@ -315,6 +320,27 @@ def ends_free_align_long_batch(queries, dbs, pairs=None, *, mode, scoring=None,
     return _align_batch(entry, queries, dbs, pairs, mode, scoring, trace_budget, cigar, device)
 
 
+def _int_xdrop(xdrop) -> int:
+    if isinstance(xdrop, bool) or not isinstance(xdrop, (int, np.integer)):
+        raise ValueError(f"xdrop {xdrop!r} is not an integer")
+    return int(xdrop)
+
+
+def xdrop_extend_long_batch(queries, dbs, pairs=None, *, xdrop, scoring=None, trace_budget: int = 0,
+                            cigar: bool = True, device: int = 0):
+    """X-drop extension (mode EXTEND with ``xdrop`` = X >= 0, the module's text)
+    of a batch of pairs of any length (saln_ends_free_xdrop_long_align_batch):
+    ends_free_align_batch(..., mode=EXTEND, xdrop=X) without the length limits,
+    with the same arguments and return.  A pair of at most 1,024 x 65,000 runs
+    the same fill as there and gives the same record, steps included; every
+    other pair runs the chunked X-drop fill, and its ``reserved`` holds the
+    row-loop steps summed over the chunks it ran (``xdrop_steps``).  The only
+    limit is the range guard, (n + m + 2) * max|parameter| + X < 2^30.  Codes
+    are sized as under ends_free_align_long_batch (``trace_bytes_long``)."""
+    return _align_batch("saln_ends_free_long_align_batch", queries, dbs, pairs, EXTEND, scoring,
+                        trace_budget, cigar, device, _int_xdrop(xdrop))
+
+
 def _one(seq1, seq2, mode, scoring, trace_budget, device, batch=ends_free_align_batch, **kw):
     res, cig = batch([seq1], [seq2], [(0, 0)], mode=mode, scoring=scoring,
                      trace_budget=trace_budget, device=device, **kw)
@@ -383,6 +409,16 @@ def extend_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device
     """extend_align for sequences of any length (ends_free_align_long_batch)."""
     return _extend(seq1, seq2, direction, scoring, trace_budget, device,
                    batch=ends_free_align_long_batch, replay=replay)
+
+
+def xdrop_extend_long(seq1, seq2, *, xdrop, scoring=None, trace_budget: int = 0, device: int = 0,
+                      direction: str = "right"):
+    """extend_align(..., xdrop=X) for sequences of any length
+    (xdrop_extend_long_batch); direction="left" as there."""
+    def batch(qs, ds, pairs, *, mode, **kw):
+        return xdrop_extend_long_batch(qs, ds, pairs, **kw)
+    return _extend(seq1, seq2, direction, scoring, trace_budget, device, batch=batch,
+                   xdrop=_int_xdrop(xdrop))
 
 
 def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
