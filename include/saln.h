@@ -142,8 +142,8 @@ int saln_abi_version(void);
  * "nw.wide_min_pairs", "nw.rows_k", "nw.stripe_pk", "nw.spec",
  * "nw.spec_passes", "nw.spec_strict", "nw.avsa_narrow", "nw.rows_lone",
  * "nw.rows_xcd", "nw.avsa_profile", "nw.pk_tab", "nw.walk_waves",
- * "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb", "ends_free.tile_rows",
- * "host.timing", "host.prefault_mb".
+ * "nw.timing_mode", "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb",
+ * "ends_free.tile_rows", "host.timing", "host.prefault_mb".
  * Two levels, no other shared state:
  *  - saln_option_*: the process registry, the default of every context;
  *  - saln_context_option_*: overrides of one context (its own thread's
@@ -303,8 +303,23 @@ int saln_nw_plan_info(const saln_nw_plan *plan, uint64_t *mask_bytes, uint64_t *
 int saln_nw_cigar_offsets(const saln_nw_plan *plan, uint64_t *cigar_off /* n_pairs+1 */);
 int saln_nw_execute(saln_nw_plan *plan, const uint8_t *d_q_seq, const uint8_t *d_db_seq,
                     saln_nw_result *d_results, uint32_t *d_cigar, void *stream);
-/* Optional per-kernel timing (hipEvents recorded on the launch stream around
- * each kernel of every execute while enabled).  Names: "nw_fill", "nw_traceback". */
+/* Optional per-kernel timing of every execute while enabled: total_ms and
+ * launches (one per execute) since it was enabled.  Names: "nw_fill" (the
+ * fill kernels), "nw_traceback" (the walk kernels), "nw_execute" (fill begin
+ * to walk end).  By default hipEvents are recorded on the launch streams
+ * around the fill and the walk launches: a span runs from marker to marker,
+ * launch latency included.  Under "nw.timing_mode" = 0 a pipelined plan of
+ * packed fill variants that walks (not score-only) has its kernels stamp the
+ * device's constant-rate wall clock themselves instead: a span runs from the first
+ * workgroup's start to the last workgroup's end of those kernels (each
+ * workgroup's first wave stamps), and the execute puts no timing event on
+ * either stream.  Such plans serve two further names:
+ * "nw_fill_gap" (fill begin of execute n+1 minus fill end of execute n, among
+ * the executes between two reads) and "nw_handoff" (walk begin minus fill
+ * end); they replace a kernel trace when the balance of the two kernels is
+ * tuned.  Every other plan keeps the events under either value.  The stamps
+ * are not the default because they cost the 150 x 150 pipelined step more
+ * than the markers do. */
 int saln_nw_plan_set_timing(saln_nw_plan *plan, int enable);
 int saln_nw_plan_kernel_time(const saln_nw_plan *plan, const char *kernel, double *total_ms,
                              uint64_t *launches);

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "nw_host.hpp"
+#include "nw_stamps.hpp"
 
 using namespace saln;
 
@@ -114,6 +115,17 @@ struct saln_nw_plan : NwPlanLayout {
     // resolved lazily (no host sync inside execute).
     std::vector<std::array<hipEvent_t, 4>> ev_pool;
     size_t ev_used = 0;
+    // stamped plans (nw_stamps.hpp stamps_supported) take no events: their
+    // kernels fold the device's wall clock into a slot of the stamp pool
+    // (blocks of kStampChunk slots, zeroed; resolve_events reads the used
+    // slots back and zeroes them again)
+    bool stamped() const {
+        return stamps_supported(var_count, async_tb, score_only, opts[Opt::TimingMode]);
+    }
+    std::vector<unsigned long long *> stamp_blocks;
+    StampBook stamps;
+    double clock_khz = 0;  // ticks per ms of the stamps' clock
+    hipError_t stamp_grow(hipStream_t s);  // one more zeroed block (s null: synchronously)
     std::map<std::string, std::pair<double, uint64_t>> ktime;
     int resolve_events();
     // the two events after the sub-batch events mark "traceback of workspace b done"
@@ -385,12 +397,25 @@ int saln_nw_cigar_offsets(const saln_nw_plan *p, uint64_t *off) {
 int saln_nw_plan_set_timing(saln_nw_plan *p, int enable) {
     if (!p) return SALN_E_INVALID;
     HIP_TRY(hipSetDevice(p->ctx->device));
-    if (p->ev_used) {
+    if (p->ev_used || p->stamps.used) {
         const int rc = p->resolve_events();
         if (rc != SALN_OK) return rc;
     }
     p->timing = enable != 0;
     p->ktime.clear();
+    // a plan whose kernels all take stamps (whatever its modes are now): the
+    // pool's first block, zeroed here, outside any timed region
+    if (p->timing && !p->stamps.blocks &&
+        stamps_supported(p->var_count, true, false, p->opts[Opt::TimingMode])) {
+        int khz = 0;
+        HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, p->ctx->device));
+        if (khz <= 0) {
+            set_error("saln_nw_plan_set_timing: the device reports no wall clock rate");
+            return SALN_E_HIP;
+        }
+        p->clock_khz = khz;
+        HIP_TRY(p->stamp_grow(nullptr));
+    }
     // the event sets of the next executes, created now rather than inside
     // them (a timed C2 step that created its four events ran 0.5 % slower,
     // round 6, profiles/r06_timing_events_ab.jsonl); more are made on demand
@@ -457,8 +482,17 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
                                       2 * (c1 - c0), s));
         }
     }
+    // timed: a stamp slot where every kernel of this execute takes one (no
+    // event, no packet of its own on either stream), else four timing events
     hipEvent_t *ev = nullptr;
-    if (p->timing) {
+    unsigned long long *stamp = nullptr;
+    if (p->timing && p->stamped()) {
+        // the pool's next block, zeroed on `s` ahead of the fills that stamp
+        // it: once per kStampChunk executes
+        if (p->stamps.full()) HIP_TRY(p->stamp_grow(s));
+        const StampBook::Slot sl = p->stamps.take();
+        stamp = p->stamp_blocks[sl.block] + sl.word;
+    } else if (p->timing) {
         if (p->ev_used == p->ev_pool.size()) {
             std::array<hipEvent_t, 4> e4{};
             for (auto &e : e4) HIP_TRY(p->own.event(&e));
@@ -470,6 +504,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
     // fills on `s`, then the walks on `t` (async: beside the next fill)
     FillExtras fx;
     fx.o = &p->opts;
+    fx.stamp = stamp;
     // async: the table fills' fallback launches go to the walk stream, behind
     // the hand-off, so nothing but the hand-off's packets sits between this
     // fill and the next one on `s` (each packet there left ~5 us idle, rocprof
@@ -496,15 +531,18 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
         HIP_TRY(launch_fill(v, p->d_pairs, a, b - a, d_q, d_db, mask, p->d_scratch, endh, p->sc,
                             p->fill_codes(v), p->var_maxld[v], s, fx));
     }
-    // the fill's end (timed: its timing event doubles as the hand-off)
+    // the fill's end (timed with events: ev[1] doubles as the hand-off;
+    // stamped or untimed: the one record without timing)
     hipEvent_t filled = ev ? ev[1] : p->sync_ev[0];
     HIP_TRY(hipEventRecord(filled, s));
     if (t != s) HIP_TRY(hipStreamWaitEvent(t, filled, 0));
     for (auto &fb : fallbacks) HIP_TRY(fb(t));
     // (async plans: the deferred fallback launches sit between ev[1] and
     // ev[2], so neither "nw_fill" nor "nw_traceback" counts them; they run
-    // only for waves whose pairs hold a byte other than A, C, G, T)
+    // only for waves whose pairs hold a byte other than A, C, G, T.  Stamped
+    // executes agree: the fallback kernel takes no stamp)
     if (ev) HIP_TRY(hipEventRecord(ev[2], t));
+    unsigned long long *const walk_stamp = stamp ? stamp + 2 : nullptr;
     for (int v = 0; v < kNumVariants; ++v) {
         const uint32_t a = p->var_first[v], b = a + p->var_count[v];
         if (a >= b) continue;
@@ -523,7 +561,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
             HIP_TRY(launch_traceback(v, p->d_pairs, a, b - a, d_q, d_db, mask, endh, ops,
                                      d_results, d_cigar, p->sc, p->stripe_layout(), t,
                                      spec ? p->d_spec_done : nullptr, p->nib[v],
-                                     walk_waves(p->opts[Opt::WalkWaves], b - a, t != s)));
+                                     walk_waves(p->opts[Opt::WalkWaves], b - a, t != s), walk_stamp));
     }
     // pairs with an empty side (boundary-only walk) ride on the traceback stream
     if (p->n_pairs > p->n_fill && p->score_only)
@@ -532,7 +570,7 @@ int saln_nw_execute(saln_nw_plan *p, const uint8_t *d_q, const uint8_t *d_db,
     else if (p->n_pairs > p->n_fill)
         HIP_TRY(launch_traceback(-1, p->d_pairs, p->n_fill, (uint32_t)(p->n_pairs - p->n_fill),
                                  d_q, d_db, mask, endh, ops, d_results, d_cigar, p->sc,
-                                 p->stripe_layout(), t));
+                                 p->stripe_layout(), t, nullptr, false, 0, walk_stamp));
     if (ev) HIP_TRY(hipEventRecord(ev[3], t));
     HIP_TRY(hipEventRecord(p->tb_done(cur), t));
     p->tb_pending[cur] = true;
@@ -663,7 +701,53 @@ int saln_nw_plan::resolve_events() {
         x.second += 1;
     }
     ev_used = 0;
+    if (!stamps.used) return SALN_OK;
+    // stamped executes: after the last one's walk, the used slots of each
+    // block (one block unless more than kStampChunk executes are pending) are
+    // read back and zeroed for their next use
+    HIP_TRY(hipEventSynchronize(tb_done(last_buf)));
+    std::vector<uint64_t> w((size_t)stamps.used * kStampWords);
+    size_t at = 0;
+    for (uint32_t b = 0; b < stamps.blocks; ++b) {
+        const size_t nb = (size_t)stamps.used_in(b) * kStampWords * sizeof(uint64_t);
+        if (!nb) break;
+        HIP_TRY(hipMemcpy(w.data() + at, stamp_blocks[b], nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(stamp_blocks[b], 0, nb));
+        at += nb / sizeof(uint64_t);
+    }
+    // (the memsets ran on the null stream, which the plan's streams do not
+    // wait for: done before the next execute can stamp)
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    StampTotals tot;
+    stamp_accumulate(w.data(), stamps.used, clock_khz, &tot);
+    stamps.reset();
+    const std::pair<const char *, const StampTotals::Sum *> names[] = {
+        {"nw_fill", &tot.fill},         {"nw_traceback", &tot.walk}, {"nw_execute", &tot.execute},
+        {"nw_fill_gap", &tot.fill_gap}, {"nw_handoff", &tot.handoff}};
+    for (const auto &nm : names) {
+        if (!nm.second->n) continue;
+        auto &k = ktime[nm.first];
+        k.first += nm.second->ms;
+        k.second += nm.second->n;
+    }
     return SALN_OK;
+}
+
+hipError_t saln_nw_plan::stamp_grow(hipStream_t s) {
+    constexpr size_t nb = (size_t)kStampChunk * kStampWords * sizeof(unsigned long long);
+    unsigned long long *b = nullptr;
+    hipError_t e = own.alloc(&b, nb);
+    if (e != hipSuccess) return e;
+    if (s) {
+        e = hipMemsetAsync(b, 0, nb, s);
+    } else {  // the null stream's memset, finished before any stream of the plan may stamp
+        e = hipMemset(b, 0, nb);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    if (e != hipSuccess) return e;
+    stamp_blocks.push_back(b);
+    stamps.grew();
+    return hipSuccess;
 }
 
 // ----------------------------------------------------------- host traceback

@@ -37,10 +37,13 @@ struct SpecArgs {
 // queued behind the table launch, for the caller to queue on the stream that
 // walks the workspace once the fills are done (pipelined plans: the fill
 // stream then runs the next step's fill without it in between).
+// stamp: the two words the packed fills of a stamped, timed execute fold their
+// span into (nw_common.hpp stamp_begin; the fallback launch is not counted).
 struct FillExtras {
     const Options *o = nullptr;
     uint32_t *bail = nullptr;
     uint32_t epoch = 0;
+    unsigned long long *stamp = nullptr;
     std::vector<std::function<hipError_t(hipStream_t)>> *deferred = nullptr;
 };
 hipError_t launch_fill(int variant, const NwPairDesc *pairs, uint32_t first, uint32_t count,
@@ -75,7 +78,8 @@ hipError_t launch_traceback(int variant, const NwPairDesc *pairs, uint32_t first
                             const int32_t *end_h, uint32_t *ops, saln_nw_result *results,
                             uint32_t *cigar, Scoring sc, int stripe_layout, hipStream_t stream,
                             const uint32_t *spec_done = nullptr, bool nib = false,
-                            uint32_t walk_waves = 0);
+                            uint32_t walk_waves = 0,
+                            unsigned long long *stamp = nullptr /* LDS and generic walks */);
 // speculative stripe walks of the plan's long column-stripe pairs: `passes`
 // walk passes, the link (accept or leave to the cooperative walker, `done`)
 // and the CIGAR copy; strict_err (SALN_SPEC_STRICT=1, tests): bit 1 set when a

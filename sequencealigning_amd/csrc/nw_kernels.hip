@@ -705,7 +705,9 @@ __global__ __launch_bounds__(256) void nw_traceback_lds_kernel(
     const NwPairDesc *__restrict__ pairs, uint32_t first, uint32_t n,
     const uint8_t *__restrict__ mask, const int32_t *__restrict__ end_h,
     uint32_t *__restrict__ ops, saln_nw_result *__restrict__ results,
-    uint32_t *__restrict__ cigar, Scoring sc, const uint8_t *__restrict__ qs) {
+    uint32_t *__restrict__ cigar, Scoring sc, const uint8_t *__restrict__ qs,
+    unsigned long long *stamp) {
+    const unsigned long long t0 = stamp_begin(stamp);
     constexpr uint32_t kWave = WalkGeo<K, kNib, G * K>::kWaveLds;
     __shared__ __attribute__((aligned(16))) uint8_t win_all[tb_lds_threads<G, K, kNib>() / 64u * kWave];
     // The walk is a latency-bound chain that shares SIMDs with the VALU-bound
@@ -730,6 +732,7 @@ __global__ __launch_bounds__(256) void nw_traceback_lds_kernel(
         const NwPairDesc p = pairs[idx];
         walk_pack_lds<G, K, kNib>(p, end_h[idx], mask, ops, results, cigar, sc, win, qs);
     }
+    stamp_end(stamp, t0);
 }
 
 // One walker per pair.  Pairs with an empty side have no mask and take the
@@ -739,13 +742,16 @@ __global__ __launch_bounds__(256) void nw_traceback_kernel(
     const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds,
     const uint8_t *__restrict__ mask, const int32_t *__restrict__ end_h,
     saln_nw_result *__restrict__ results, uint32_t *__restrict__ cigar, Scoring sc,
-    GeomTable gt) {
+    GeomTable gt, unsigned long long *stamp) {
+    const unsigned long long t0 = stamp_begin(stamp);
     const uint32_t idx = first + blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= first + n) return;
-    const NwPairDesc p = pairs[idx];
-    const Geom geo = gt.g[p.variant];
-    walk_pair(p, p.len_q && p.len_db ? end_h[idx] : hs_boundary_end(sc, p.len_q, p.len_db), qs,
-              ds, mask, geo, results, cigar, sc);
+    if (idx < first + n) {
+        const NwPairDesc p = pairs[idx];
+        const Geom geo = gt.g[p.variant];
+        walk_pair(p, p.len_q && p.len_db ? end_h[idx] : hs_boundary_end(sc, p.len_q, p.len_db),
+                  qs, ds, mask, geo, results, cigar, sc);
+    }
+    stamp_end(stamp, t0);
 }
 
 // ------------------------------------------------ render batches: next event
@@ -2223,8 +2229,11 @@ __device__ __forceinline__ int fill_pk_body(Src src, uint32_t count, const uint8
 template <int G, int K, int kCodes, typename Src, int KS, bool kRebase = false>
 __global__ __launch_bounds__(256, (pk_min_waves<G, K, kCodes>())) void nw_fill_pk_kernel(
     Src src, uint32_t count, const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds,
-    uint8_t *__restrict__ mask, Scoring sc, uint32_t ld_max, bool sc_steady) {
+    uint8_t *__restrict__ mask, Scoring sc, uint32_t ld_max, bool sc_steady,
+    unsigned long long *stamp) {
+    const unsigned long long t0 = stamp_begin(stamp);
     fill_pk_body<G, K, kCodes, Src, KS, kRebase>(src, count, qs, ds, mask, sc, ld_max, sc_steady);
+    stamp_end(stamp, t0);
 }
 
 // 4-bit walk codes with table penalties (kTabMode 1, nw.pk_tab), and the
@@ -2239,7 +2248,8 @@ template <int G, int K, typename Src, int kScale = 2, int kCodes = kCodesNib>
 __global__ __launch_bounds__(256, (pk_min_waves<G, K, kCodes>())) void nw_fill_pk_tab_kernel(
     Src src, uint32_t count, const uint8_t *__restrict__ qs, const uint8_t *__restrict__ ds,
     uint8_t *__restrict__ mask, Scoring sc, uint32_t ld_max, uint32_t *__restrict__ bail,
-    uint32_t epoch) {
+    uint32_t epoch, unsigned long long *stamp) {
+    const unsigned long long t0 = stamp_begin(stamp);
     // kScale: 2 or 4 (the value scale); 3: scale 2 with row profiles (kTabMode 5)
     // (issue priority 2: between a pipelined walk's first pairs and its
     // later ones, nw_traceback_lds_kernel)
@@ -2248,6 +2258,7 @@ __global__ __launch_bounds__(256, (pk_min_waves<G, K, kCodes>())) void nw_fill_p
                                 kScale == 4 ? 4 : kScale == 3 ? 5 : 1>(src, count, qs, ds, mask,
                                                                        sc, ld_max, true);
     if (__builtin_amdgcn_ballot_w64(st == 1) && (threadIdx.x & 63u) == 0) *bail = epoch;
+    stamp_end(stamp, t0);
 }
 // (kRebaseGeneric: the fallback of a launch whose dbs need the rebasing frame;
 // the extension-free table body has no drift and needs none)
@@ -3386,7 +3397,7 @@ static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uin
                     if (e == hipSuccess) e = allow_lds((const void *)fk, lds_tab);
                     if (e != hipSuccess) return e;
                     tk<<<grid, dim3(256), lds_tab, s>>>(src, count, qs, ds, mask, sc, ld_max,
-                                                        fx.bail, fx.epoch);
+                                                        fx.bail, fx.epoch, fx.stamp);
                     auto fb = [=, bail = fx.bail, epoch = fx.epoch](hipStream_t fs) {
                         fk<<<dim3(std::min(grid.x, kTabFbBlocks)), dim3(256), lds_tab, fs>>>(
                             src, count, qs, ds, mask, sc, ld_max, bail, epoch, grid.x);
@@ -3404,7 +3415,7 @@ static hipError_t fill_pk(dim3 grid, hipStream_t s, const NwPairDesc *pairs, uin
         const auto kern = nw_fill_pk_kernel<G, K, kC, PlanSrc, KS, kRb>;
         const hipError_t e = allow_lds((const void *)kern, lds);
         if (e != hipSuccess) return e;
-        kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, mask, sc, ld_max, true);
+        kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, mask, sc, ld_max, true, fx.stamp);
         return hipSuccess;
     };
     return dispatch_bool(fp.rebase, [&](auto rebase_c) {
@@ -3441,7 +3452,7 @@ static hipError_t avsa_pk(const AvsaSrc &src, uint32_t count, const uint8_t *qs,
         const auto kern = nw_fill_pk_kernel<G, K, kCodesNone, AvsaSrc, K, decltype(rebase_c)::value>;
         const hipError_t e = allow_lds((const void *)kern, lds);
         if (e != hipSuccess) return e;
-        kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, nullptr, sc, ld_max, true);
+        kern<<<grid, dim3(256), lds, s>>>(src, count, qs, ds, nullptr, sc, ld_max, true, nullptr);
         return hipSuccess;
     });
 }
@@ -3593,14 +3604,15 @@ hipError_t launch_traceback(int variant, const NwPairDesc *pairs, uint32_t first
                             const uint8_t *qs, const uint8_t *ds, const uint8_t *mask,
                             const int32_t *end_h, uint32_t *ops, saln_nw_result *results,
                             uint32_t *cigar, Scoring sc, int stripe_layout, hipStream_t stream,
-                            const uint32_t *spec_done, bool nib, uint32_t walk_waves) {
+                            const uint32_t *spec_done, bool nib, uint32_t walk_waves,
+                            unsigned long long *stamp) {
     if (n == 0) return hipSuccess;
     if (nib && !(variant_in_range(variant) && variant_nib(variant))) return hipErrorInvalidValue;
     if (variant < 0) {  // empty-side pairs
         GeomTable gt;
         for (int v = 0; v < kNumVariants; ++v) gt.g[v] = kVariantTable[v].g;
         nw_traceback_kernel<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(
-            pairs, first, n, qs, ds, mask, end_h, results, cigar, sc, gt);
+            pairs, first, n, qs, ds, mask, end_h, results, cigar, sc, gt, stamp);
         return hipGetLastError();
     }
     const hipError_t e = dispatch_variant(variant, [&](auto g_c, auto k_c, auto v_c) -> hipError_t {
@@ -3611,7 +3623,7 @@ hipError_t launch_traceback(int variant, const NwPairDesc *pairs, uint32_t first
             uint32_t blocks = (n + nt - 1) / nt;
             if (waves) blocks = std::min(blocks, std::max(1u, waves / (nt / 64u)));
             nw_traceback_lds_kernel<G, K, kNib><<<dim3(blocks), dim3(nt), 0, stream>>>(
-                pairs, first, n, mask, end_h, ops, results, cigar, sc, qs);
+                pairs, first, n, mask, end_h, ops, results, cigar, sc, qs, stamp);
             return hipSuccess;
         };
         (void)walk;

@@ -62,7 +62,13 @@ def main():
     plan.check()
     f, fn = plan.kernel_time("nw_fill") if not a.no_timing else (0.0, 1)
     tb, tn = plan.kernel_time("nw_traceback") if not a.no_timing else (0.0, 1)
+    # stamped plans only (device-side stamps): the fill stream's idle time
+    # between two fills and the fill -> walk hand-off, in us
+    gap, gn = plan.kernel_time("nw_fill_gap")
+    ho, hn = plan.kernel_time("nw_handoff")
     print(json.dumps({"tag": a.tag, "lib": os.path.basename(_lib.LIB_PATH), "opts": a.opt,
+                      "fill_gap_us": round(gap / gn * 1e3, 2) if gn else None,
+                      "handoff_us": round(ho / hn * 1e3, 2) if hn else None,
                       "timing": not a.no_timing,
                       "pipeline": a.pipeline, "full": a.full,
                       "gcups": round(plan.cells / dt / 1e9, 1), "ms_per_step": round(dt * 1e3, 4),
