@@ -871,6 +871,18 @@ int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes)
  * 64 x 8, 64 x 16: the smallest that holds the query).  SALN_E_INVALID above
  * 1,024 columns.  The launch code asks the same function. */
 int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols_per_lane);
+/* Host only: the workgroup of the class fill that runs queries of len_q
+ * columns in a launch whose longest db has ld_max rows (a batch's pairs are
+ * cut into launches by class and by the power-of-two bucket of the db length).
+ * *groups: the lane groups, one pair each, of a workgroup: 256 / lanes of
+ * them, lowered until their staged db rows, groups * (ld_max + 2 * lanes)
+ * bytes, fit 64 KB; with has_matrix != 0 (the saln_ends_free_sub_* entry
+ * points) 64 KB less the matrix's block of 1,408 bytes; never below 1.
+ * *lds_bytes: those bytes of staged rows (the block not counted).  A workgroup
+ * has *groups * lanes lanes.  SALN_E_INVALID for a NULL output, above 1,024
+ * columns and above 65,000 rows.  The launch code asks the same function. */
+int saln_ends_free_fill_geometry(uint64_t len_q, uint64_t ld_max, int has_matrix, uint32_t *groups,
+                                 uint32_t *lds_bytes);
 
 /* X-drop extension: SALN_MODE_EXTEND with one more rule and a parameter
  * xdrop = X >= 0.  Borders, recurrences, tie rules and the walk are

@@ -150,6 +150,7 @@ EXPORTS = [
     "saln_ends_free_align_batch", "saln_ends_free_aln_count", "saln_ends_free_aln_get",
     "saln_ends_free_aln_free", "saln_ends_free_plan_create", "saln_ends_free_execute",
     "saln_ends_free_plan_destroy", "saln_ends_free_trace_bytes", "saln_ends_free_pair_geometry",
+    "saln_ends_free_fill_geometry",
     "saln_ends_free_long_align_batch", "saln_ends_free_long_trace_bytes",
     "saln_ends_free_long_pair_path",
     "saln_ends_free_replay_align_batch", "saln_ends_free_replay_bytes",
@@ -319,6 +320,7 @@ def lib() -> C.CDLL:
         L.saln_ends_free_plan_destroy.argtypes = [vp]
         L.saln_ends_free_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
         L.saln_ends_free_pair_geometry.argtypes = [C.c_uint64, u32p, u32p]
+        L.saln_ends_free_fill_geometry.argtypes = [C.c_uint64, C.c_uint64, C.c_int, u32p, u32p]
         L.saln_ends_free_long_align_batch.argtypes = L.saln_ends_free_align_batch.argtypes
         L.saln_ends_free_long_trace_bytes.argtypes = [C.c_uint64, C.c_uint64, u64p]
         L.saln_ends_free_long_pair_path.argtypes = [C.c_uint64, C.c_uint64,

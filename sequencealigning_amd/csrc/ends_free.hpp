@@ -188,6 +188,23 @@ inline uint64_t ef_lds_bytes(int cls, uint32_t groups, uint32_t ld_max) {
     return (uint64_t)groups * ((uint64_t)ld_max + 2u * (uint32_t)kEfClass[cls].lanes);
 }
 
+// The workgroup of a class fill whose longest db has ld_max rows: as many lane
+// groups (of at most 256 lanes together) as 64 KB of LDS stage rows for.  The
+// matrix block comes out of the same 64 KB; a single group's row of the
+// longest dbs goes up to kEfSubBytes above them, far below a CU's LDS.  The
+// one place the decision is made: saln_ends_free_fill_geometry and the launch
+// both ask it.
+struct EfFillGeometry {
+    uint32_t groups;
+    uint64_t lds_bytes;  // ef_lds_bytes of them: the launch's dynamic LDS
+};
+inline EfFillGeometry ef_fill_geometry(int cls, uint32_t ld_max, bool has_matrix) {
+    const uint64_t budget = (64u << 10) - (has_matrix ? kEfSubBytes : 0u);
+    uint32_t groups = 256u / (uint32_t)kEfClass[cls].lanes;
+    while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > budget) --groups;
+    return EfFillGeometry{groups, ef_lds_bytes(cls, groups, ld_max)};
+}
+
 // Every fill below takes `sub` after the scoring: nullptr runs the
 // match / mismatch instances and reads sc whole; a device block of kEfSubBytes
 // (above) runs the kSub instances, which read sc.open and sc.extend only.

@@ -244,6 +244,17 @@ int saln_ends_free_pair_geometry(uint64_t len_q, uint32_t *lanes, uint32_t *cols
     return SALN_OK;
 }
 
+int saln_ends_free_fill_geometry(uint64_t len_q, uint64_t ld_max, int has_matrix, uint32_t *groups,
+                                 uint32_t *lds_bytes) {
+    if (!groups || !lds_bytes) return SALN_E_INVALID;
+    const int rc = check_pair(len_q, ld_max, 0);
+    if (rc != SALN_OK) return rc;
+    const EfFillGeometry g = ef_fill_geometry(ef_class_of(len_q), (uint32_t)ld_max, has_matrix != 0);
+    *groups = g.groups;
+    *lds_bytes = (uint32_t)g.lds_bytes;
+    return SALN_OK;
+}
+
 int saln_ends_free_trace_bytes(uint64_t len_q, uint64_t len_db, uint64_t *bytes) {
     if (!bytes) return SALN_E_INVALID;
     const int rc = check_pair(len_q, len_db, 0);

@@ -382,13 +382,9 @@ hipError_t launch_ef_fill(int cls, int32_t mode, const EfPair *pairs, uint32_t f
     if (count == 0) return hipSuccess;
     if (cls < 0 || cls >= kEfClasses || ld_max > kEfMaxDb) return hipErrorInvalidValue;
     const uint32_t G = (uint32_t)kEfClass[cls].lanes;
-    // as many groups per workgroup (of at most 256 lanes) as 64 KB of LDS stage rows for
-    // (the matrix block comes out of the same 64 KB; a single group's row of
-    // the longest dbs goes up to kEfSubBytes above them, far below a CU's LDS)
-    const uint64_t budget = (64u << 10) - (sub ? kEfSubBytes : 0u);
-    uint32_t groups = 256u / G;
-    while (groups > 1 && ef_lds_bytes(cls, groups, ld_max) > budget) --groups;
-    const size_t lds = (size_t)ef_lds_bytes(cls, groups, ld_max);
+    const EfFillGeometry geo = ef_fill_geometry(cls, ld_max, sub != nullptr);
+    const uint32_t groups = geo.groups;
+    const size_t lds = (size_t)geo.lds_bytes;
     const FillLaunch a{mode, dim3((count + groups - 1) / groups), dim3(groups * G), lds, s, pairs, first, count,
                        qs, ds, codes, end_state, results, sc, ld_max, sub, xdrop};
     switch (cls) {

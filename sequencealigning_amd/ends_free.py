@@ -554,6 +554,20 @@ def pair_geometry(len_q: int) -> tuple[int, int]:
     return lanes.value, cols.value
 
 
+def fill_geometry(len_q: int, ld_max: int, has_matrix: bool = False) -> tuple[int, int]:
+    """saln_ends_free_fill_geometry: (lane groups per workgroup, bytes of LDS
+    their staged db rows take) of the class fill that runs queries of len_q
+    columns in a launch whose longest db has ld_max rows (host only);
+    has_matrix: under a SubstitutionMatrix, whose block shares the 64 KB.  A
+    workgroup has groups * pair_geometry(len_q)[0] lanes.  Raises SalnError
+    (E_INVALID) above MAX_QUERY columns or 65,000 rows."""
+    groups, lds = C.c_uint32(), C.c_uint32()
+    _lib.check(_lib.lib().saln_ends_free_fill_geometry(int(len_q), int(ld_max), int(bool(has_matrix)),
+                                                       C.byref(groups), C.byref(lds)),
+               "saln_ends_free_fill_geometry")
+    return groups.value, lds.value
+
+
 class EndsFreePlan:
     """Device-resident score-only batch: plan from host offsets and a pair
     list once, execute on device (torch) sequence buffers into a device tensor
