@@ -930,8 +930,8 @@ int saln_ends_free_fill_geometry(uint64_t len_q, uint64_t ld_max, int has_matrix
  * The entry points are their plain counterparts without `mode` and with
  * xdrop; saln_ends_free_execute / _plan_destroy and saln_ends_free_aln_count /
  * _get / _free serve them unchanged.  Pairs above the limits:
- * saln_ends_free_xdrop_long_align_batch, below.  The tiled replay has no X-drop
- * form. */
+ * saln_ends_free_xdrop_long_align_batch, below, and its tiled-replay form
+ * saln_ends_free_xdrop_replay_align_batch. */
 int saln_ends_free_xdrop_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
                                      uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
                                      uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
@@ -1053,6 +1053,60 @@ int saln_ends_free_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, c
  * saln_ends_free_long_pair_path, and for an R outside the five values. */
 int saln_ends_free_replay_bytes(uint64_t len_q, uint64_t len_db, uint32_t tile_rows, uint64_t *bytes);
 
+/* X-drop extension of long pairs with their CIGARs by tiled replay
+ * (ends_free_xdrop_replay_kernels.hip, ends_free_replay_host.cpp).
+ * saln_ends_free_xdrop_replay_align_batch is
+ * saln_ends_free_xdrop_long_align_batch with another way to the words of a
+ * pair of the chunked path: the same arguments, handle and refusals (a negative
+ * xdrop, a pair outside the range guard with X, a NULL matrix), and option
+ * "ends_free.tile_rows" outside 64, 128, 256, 512, 1024 is SALN_E_INVALID too;
+ * all before the device is touched.  Records (all fields but `reserved`) and
+ * words are the same, word for word.
+ *  - A pair within the class limits runs the class X-drop fill and the
+ *    ordinary walk, as under the other X-drop entry points, steps included.
+ *  - A pair of the chunked path is filled score only by the keep form of the
+ *    chunked X-drop fill.  Per chunk that ran it keeps a header (the window of
+ *    rows lo_c .. z_c the chunk ran, and B above the window), the boundary
+ *    column's entries (P, I, B) of those rows and, for every R-th db row inside
+ *    the window, a checkpoint row (P, the next row's D, and B of every
+ *    column).  Every chunk runs on until its last lane has run row max(last
+ *    live row, lo_c), so every kept row of a window is whole.
+ *  - The rounds are the replay's: a wave fills again the codes of the rows of
+ *    one tile that lie inside the chunk's window, from the checkpoint row above
+ *    them or, where the window starts in the tile, from the fill's own start,
+ *    with the X-drop rule (B is part of the kept state, so the cells are the
+ *    same integers); the extension walk follows them unchanged, since it never
+ *    reads a pruned cell.  The tile fill reads no entry outside the windows
+ *    the headers state: what lies there is stale memory.  chunks + row blocks
+ *    - 1 rounds of the largest pair are queued and none is waited for; a pair
+ *    unfinished after them has SALN_INTERNAL and no words (never expected).
+ *  - `reserved`: the forward pass's row-loop steps, per chunk at most (its
+ *    rows) + 63 + 1; the tile fills are not counted.  It need not equal the
+ *    long entry point's value: the last chunk drains as the others do.
+ *  - trace_budget_bytes bounds a chunk's sum of
+ *    saln_ends_free_xdrop_replay_bytes; a pair whose footprint alone exceeds it
+ *    gets score, ends, SALN_TRACE_CAP, begins -1 and no words.
+ *  - want_cigar == 0: the long X-drop entry point's fill.
+ * No boundary workspace: a pair's columns lie in its own footprint, and a
+ * launch runs min(pairs, 4,096) waves. */
+int saln_ends_free_xdrop_replay_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off,
+                                            uint64_t n_q, const uint8_t *db_seq, const uint64_t *db_off,
+                                            uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db,
+                                            uint64_t n_pairs, const saln_nw_scoring *scoring, int32_t xdrop,
+                                            uint64_t trace_budget_bytes, int want_cigar,
+                                            saln_ends_free_aln **out);
+/* Host only: the bytes one pair holds against trace_budget_bytes under the
+ * X-drop replay entry points, the one place they are computed (the batch's
+ * chunking asks it).  tile_rows: R, or 0 for the process registry's option
+ * value.  A pair within the class limits: saln_ends_free_trace_bytes.  Every
+ * other pair, with chunks = ceil(len_q / 1024): chunks * 16 (a header per
+ * chunk) + (chunks - 1) * len_db * 16 (boundary columns: P, I, B)
+ * + floor((len_db - 1) / R) * chunks * 1024 * 16 (checkpoint rows: P, D, B)
+ * + R * 512 (the tile in work); 0 when a sequence is empty.  The size is for
+ * all rows: the windows are not known before the fill.  SALN_E_INVALID as
+ * saln_ends_free_replay_bytes. */
+int saln_ends_free_xdrop_replay_bytes(uint64_t len_q, uint64_t len_db, uint32_t tile_rows, uint64_t *bytes);
+
 /* Ends-free alignment under a substitution matrix (protein scoring under a
  * BLOSUM or PAM style table, IUPAC nucleotide codes, transition /
  * transversion scoring).  Everything above stays as it is written: the
@@ -1136,6 +1190,14 @@ int saln_ends_free_sub_xdrop_long_align_batch(saln_context *ctx, const uint8_t *
                                               const saln_sub_matrix *matrix, int32_t xdrop,
                                               uint64_t trace_budget_bytes, int want_cigar,
                                               saln_ends_free_aln **out);
+/* saln_ends_free_xdrop_replay_align_batch (above) under a matrix. */
+int saln_ends_free_sub_xdrop_replay_align_batch(saln_context *ctx, const uint8_t *q_seq,
+                                                const uint64_t *q_off, uint64_t n_q, const uint8_t *db_seq,
+                                                const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                                const uint32_t *pair_db, uint64_t n_pairs,
+                                                const saln_sub_matrix *matrix, int32_t xdrop,
+                                                uint64_t trace_budget_bytes, int want_cigar,
+                                                saln_ends_free_aln **out);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

@@ -159,6 +159,8 @@ EXPORTS = [
     "saln_ends_free_xdrop_align_batch", "saln_ends_free_sub_xdrop_align_batch",
     "saln_ends_free_xdrop_plan_create", "saln_ends_free_sub_xdrop_plan_create",
     "saln_ends_free_xdrop_long_align_batch", "saln_ends_free_sub_xdrop_long_align_batch",
+    "saln_ends_free_xdrop_replay_align_batch", "saln_ends_free_sub_xdrop_replay_align_batch",
+    "saln_ends_free_xdrop_replay_bytes",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -342,6 +344,8 @@ def lib() -> C.CDLL:
             getattr(L, name + "align_batch").argtypes = list(batch[:10]) + [batch[11], C.c_int32] + list(batch[12:])
             getattr(L, name + "plan_create").argtypes = list(plan[:8]) + [plan[9], C.c_int32, plan[10]]
             getattr(L, name + "long_align_batch").argtypes = getattr(L, name + "align_batch").argtypes
+            getattr(L, name + "replay_align_batch").argtypes = getattr(L, name + "align_batch").argtypes
+        L.saln_ends_free_xdrop_replay_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u64p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

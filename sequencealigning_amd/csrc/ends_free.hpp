@@ -168,6 +168,33 @@ __host__ __device__ inline EfReplayLayout ef_replay_layout(uint64_t lq, uint64_t
     l.bytes = l.tile + R * kEfTileRowBytes;
     return l;
 }
+// The same for the X-drop extension (ends_free_xdrop_replay_kernels.hip,
+// saln_ends_free_xdrop_replay_*): every entry also holds
+// B, one int4 each, and a header per chunk tells which rows the chunk ran.
+//   hdr    one int4 per chunk: (lo_c, z_c, Bs = B(lo_c - 1, .), 1), or all 0 for
+//          a chunk that did not run
+//   cols   the boundary columns 0 .. chunks - 2: (P(r, c0), I(r, c0 + 1),
+//          B(r, c0), 0), the chunked X-drop fill's entries, ld each
+//   cps    the checkpoint rows: (P(r, j), D(r + 1, j), B(r, j), 0), chunks * 1024 each
+//   tile   the codes of the tile in work
+// Only the rows lo_c .. z_c of a chunk that ran are written (columns: of chunk
+// c's own window); everything else in the area is stale memory, and the tile
+// fill reads nothing outside them.  All four are multiples of 16 bytes; the
+// area itself starts 16-byte aligned (ef_align_batch).
+struct EfXdropReplayLayout {
+    uint64_t hdr, cols, cps, tile, bytes;
+};
+__host__ __device__ inline EfXdropReplayLayout ef_xdrop_replay_layout(uint64_t lq, uint64_t ld, uint64_t R) {
+    if (lq == 0 || ld == 0) return EfXdropReplayLayout{0, 0, 0, 0, 0};
+    const uint64_t chunks = (lq + kEfChunkCols - 1) / kEfChunkCols;
+    EfXdropReplayLayout l;
+    l.hdr = 0;
+    l.cols = chunks * 16;
+    l.cps = l.cols + (chunks - 1) * ld * kEfXdropBndBytes;
+    l.tile = l.cps + (ld - 1) / R * chunks * kEfChunkCols * 16;
+    l.bytes = l.tile + R * kEfTileRowBytes;
+    return l;
+}
 inline bool ef_tile_rows_ok(int64_t R) {
     return R == 64 || R == 128 || R == 256 || R == 512 || R == 1024;
 }
@@ -261,6 +288,18 @@ hipError_t launch_ef_tile_walk(int32_t mode, const EfPair *pairs, uint32_t count
                                const uint8_t *ds, const uint8_t *area, uint32_t tile_rows,
                                saln_ends_free_result *results, uint32_t *words, uint32_t *lens,
                                EfWalkState *state, hipStream_t s);
+// The X-drop forms of the forward pass and of the tile fill (SALN_MODE_EXTEND,
+// xdrop = X >= 0; ends_free_xdrop_replay_kernels.hip): the area is
+// ef_xdrop_replay_layout's, the records' `reserved` holds the forward pass's
+// row-loop steps, and the walk is launch_ef_replay_start / launch_ef_tile_walk.
+hipError_t launch_ef_xdrop_fill_keep(const EfPair *pairs, uint32_t first, uint32_t count, const uint8_t *qs,
+                                     const uint8_t *ds, EfScoring sc, const uint8_t *sub, int32_t xdrop,
+                                     uint8_t *area, uint32_t tile_rows, uint8_t *end_state,
+                                     saln_ends_free_result *results, uint32_t slots, uint32_t *counter,
+                                     hipStream_t s);
+hipError_t launch_ef_xdrop_tile_fill(const EfPair *pairs, uint32_t count, const uint8_t *qs, const uint8_t *ds,
+                                     EfScoring sc, const uint8_t *sub, int32_t xdrop, uint8_t *area,
+                                     uint32_t tile_rows, const EfWalkState *state, hipStream_t s);
 // Walk of pairs[0 .. count): one pair per lane, from the end cell the fill
 // reported.  A pair's words end at words[cig_off + lq + ld), cigar_len of
 // them (also in lens, indexed like pairs).

@@ -112,16 +112,16 @@ int make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::
     return SALN_OK;
 }
 
-// An X-drop call's X (kEfNoXdrop: none): >= 0, extension only, and not under
-// the tiled replay (the class fills and the chunked fill have X-drop forms).
-int check_xdrop(int32_t xdrop, int32_t mode, bool replay) {
+// An X-drop call's X (kEfNoXdrop: none): >= 0, and extension only (the class
+// fills, the chunked fill and the tiled replay have X-drop forms).
+int check_xdrop(int32_t xdrop, int32_t mode) {
     if (xdrop == kEfNoXdrop) return SALN_OK;
     if (xdrop < 0) {
         set_error("ends_free: xdrop " + std::to_string(xdrop) + " is negative (X >= 0)");
         return SALN_E_INVALID;
     }
-    if (mode != SALN_MODE_EXTEND || replay) {
-        set_error("ends_free: X-drop is part of SALN_MODE_EXTEND, and the tiled replay has no X-drop form");
+    if (mode != SALN_MODE_EXTEND) {
+        set_error("ends_free: X-drop is part of SALN_MODE_EXTEND");
         return SALN_E_INVALID;
     }
     return SALN_OK;
@@ -158,10 +158,13 @@ uint64_t code_bytes(uint64_t lq, uint64_t ld) {
 }
 
 // The same under the long entry points, which own the long layout's size, and
-// (tile_rows != 0) under the replay entry point, which owns the footprint.
-uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok, uint32_t tile_rows) {
+// (tile_rows != 0) under the replay entry points, which own the footprints
+// (xdrop: the X-drop form's).
+uint64_t code_bytes(uint64_t lq, uint64_t ld, bool long_ok, uint32_t tile_rows, bool xdrop) {
     uint64_t bytes = 0;
     if (!long_ok) return code_bytes(lq, ld);
+    if (tile_rows && xdrop)
+        return saln_ends_free_xdrop_replay_bytes(lq, ld, tile_rows, &bytes) == SALN_OK ? bytes : 0;
     if (tile_rows) return saln_ends_free_replay_bytes(lq, ld, tile_rows, &bytes) == SALN_OK ? bytes : 0;
     return saln_ends_free_long_trace_bytes(lq, ld, &bytes) == SALN_OK ? bytes : 0;
 }
@@ -357,7 +360,7 @@ int saln::ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
     uint64_t max_abs = 0;
     std::vector<uint8_t> block;
     int rc = check_mode(mode);
-    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, false);
+    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode);
     if (rc == SALN_OK) rc = make_scoring(scoring, &p->sc, &max_abs, &block);
     std::vector<EfPair> pairs;
     if (rc == SALN_OK)
@@ -404,7 +407,9 @@ int saln_ends_free_plan_destroy(saln_ends_free_plan *p) {
 // chunked fill for the pairs the classes refuse.  saln_ends_free_replay_align_batch
 // (long_ok and tile_rows != 0): a chunk's bytes are the pairs' replay
 // footprints, and its pairs of the chunked path run ef_replay_run in place of
-// the fill with codes and ef_walk_kernel.
+// the fill with codes and ef_walk_kernel.  With an X on top
+// (saln_ends_free_xdrop_replay_align_batch) the footprints are the X-drop
+// form's, 16-byte aligned, and ef_replay_run takes the X.
 int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                          const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
                          const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
@@ -417,7 +422,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     uint64_t max_abs = 0;
     std::vector<uint8_t> block;
     int rc = check_mode(mode);
-    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode, tile_rows != 0);
+    if (rc == SALN_OK) rc = check_xdrop(xdrop, mode);
     if (rc == SALN_OK) rc = make_scoring(scoring, &sc, &max_abs, &block);
     std::vector<EfPair> all;
     if (rc == SALN_OK)
@@ -443,16 +448,21 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
     std::vector<uint8_t> capped(n_pairs, 0), unfinished(tile_rows ? n_pairs : 0, 0);
     for (uint64_t k = 0; k < n_pairs; ++k) {
         EfPair p = all[k];
-        const uint64_t bytes = code_bytes(p.lq, p.ld, long_ok, tile_rows);
+        const uint64_t bytes = code_bytes(p.lq, p.ld, long_ok, tile_rows, xdrop != kEfNoXdrop);
         if (!want_cigar || bytes > budget) {
             capped[k] = want_cigar ? 1 : 0;
             plain.pairs.push_back(p);
             continue;
         }
-        if (chunks.empty() || chunks.back().bytes + bytes > budget ||
+        // an X-drop replay area holds int4 entries: it starts 16-byte aligned
+        // (class codes before it in the chunk are multiples of 8 only)
+        const uint64_t align = tile_rows && xdrop != kEfNoXdrop && ef_path_of(p.lq, p.ld, true) == kEfLongClass
+                                   ? 15u : 0u;
+        if (chunks.empty() || ((chunks.back().bytes + align) & ~align) + bytes > budget ||
             chunks.back().pairs.size() >= (1u << 30))
             chunks.emplace_back();
         Chunk &c = chunks.back();
+        c.bytes = (c.bytes + align) & ~align;
         p.code_off = c.bytes;
         p.cig_off = c.words;
         c.bytes += bytes;
@@ -532,7 +542,7 @@ int saln::ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t
         if (n_walk < n) {
             rc = ef_replay_run(&rws, mode, c.pairs.data() + n_walk, d_pairs.as<EfPair>() + n_walk, n - n_walk,
                                sq, sd, sc, sub, d_codes.as<uint8_t>(), tile_rows, d_state.as<uint8_t>(), results,
-                               d_words.as<uint32_t>(), d_lens.as<uint32_t>() + n_walk, s);
+                               d_words.as<uint32_t>(), d_lens.as<uint32_t>() + n_walk, s, xdrop);
             if (rc != SALN_OK) return rc;
         }
         lens.resize(n);

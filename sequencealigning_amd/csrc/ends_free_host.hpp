@@ -28,8 +28,10 @@ struct EfScoreSrc {
 // kEfNoXdrop, or the X of saln_ends_free_xdrop_align_batch (mode
 // SALN_MODE_EXTEND, long_ok false: the class fills' X-drop instances) and of
 // saln_ends_free_xdrop_long_align_batch (long_ok true, tile_rows 0: pairs
-// above the limits run the chunked X-drop fill, ef_xdrop_long_fill).  The
-// replay has no X-drop form: tile_rows != 0 with an X is refused.
+// above the limits run the chunked X-drop fill, ef_xdrop_long_fill) and of
+// saln_ends_free_xdrop_replay_align_batch (long_ok true, tile_rows != 0: a
+// chunk holds X-drop replay footprints, ef_xdrop_replay_layout, and
+// ef_replay_run takes the X).
 // ends_free_host.cpp.
 int ef_align_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
                    const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
@@ -71,11 +73,13 @@ int ef_xdrop_long_fill(EfLongWorkspace *ws, const EfPair *d_pairs, uint32_t firs
                        saln_ends_free_result *d_results, hipStream_t s);
 
 // Device workspace of a batch's replays, all on one stream: the walks' states
-// and the forward pass's pair counter.
+// and the forward pass's pair counter; under X-drop also the walk's own pair
+// descriptors (ef_replay_run), on the host and on the device.
 struct EfReplayWorkspace {
-    DevBuf state, counter;
-    size_t state_bytes = 0;
-    EfReplayWorkspace(saln_context *ctx, hipStream_t s) : state(ctx, s), counter(ctx, s) {}
+    DevBuf state, counter, walk_pairs;
+    size_t state_bytes = 0, walk_pairs_bytes = 0;
+    std::vector<EfPair> walk_pairs_host;
+    EfReplayWorkspace(saln_context *ctx, hipStream_t s) : state(ctx, s), counter(ctx, s), walk_pairs(ctx, s) {}
 };
 
 // What ef_replay_run leaves in lens for a pair whose walk did not end within
@@ -86,10 +90,14 @@ constexpr uint32_t kEfWalkUnfinished = 0xFFFFFFFFu;
 // d_pairs the same on the device; code_off: each pair's replay area in
 // d_area): the forward pass, then the rounds of tile fill and tile walk, all
 // queued on s, none waited for.  Records, words and lens as the class walk
-// leaves them.  ends_free_replay_host.cpp.
+// leaves them.  xdrop: kEfNoXdrop, or X with SALN_MODE_EXTEND: the X-drop
+// forward pass and tile fill over ef_xdrop_replay_layout's areas (code_off a
+// multiple of 16), the forward pass's steps in `reserved`.
+// ends_free_replay_host.cpp.
 int ef_replay_run(EfReplayWorkspace *ws, int32_t mode, const EfPair *h_pairs, const EfPair *d_pairs,
                   uint32_t count, const uint8_t *d_q, const uint8_t *d_db, const EfScoring &sc,
                   const uint8_t *d_sub, uint8_t *d_area, uint32_t tile_rows, uint8_t *d_end_state,
-                  saln_ends_free_result *d_results, uint32_t *d_words, uint32_t *d_lens, hipStream_t s);
+                  saln_ends_free_result *d_results, uint32_t *d_words, uint32_t *d_lens, hipStream_t s,
+                  int32_t xdrop = kEfNoXdrop);
 
 }  // namespace saln

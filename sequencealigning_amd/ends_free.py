@@ -40,7 +40,11 @@ length is ``xdrop_extend_long_batch`` / ``xdrop_extend_long``
 (``saln_ends_free_xdrop_long_*``): a pair above the limits runs the chunked
 X-drop fill (ends_free_xdrop_long_kernels.hip), which runs a chunk of 1,024
 query columns only over the rows between its first and last unpruned cell and
-leaves the pair at the first chunk without one.
+leaves the pair at the first chunk without one.  With ``replay=True`` they
+call ``saln_ends_free_xdrop_replay_align_batch``: such a pair keeps, for the
+rows each chunk ran, boundary columns and checkpoint rows (with B) in place of
+its codes, and its words come from the tiled replay
+(ends_free_xdrop_replay_kernels.hip; ``xdrop_replay_bytes``).
 
 The definitions (recurrences, tie rules, the walk's fixed choices) are in
 include/saln.h and DESIGN.md; the checker of the four modes under both kinds
@@ -327,7 +331,7 @@ def _int_xdrop(xdrop) -> int:
 
 
 def xdrop_extend_long_batch(queries, dbs, pairs=None, *, xdrop, scoring=None, trace_budget: int = 0,
-                            cigar: bool = True, device: int = 0):
+                            cigar: bool = True, device: int = 0, replay: bool = False):
     """X-drop extension (mode EXTEND with ``xdrop`` = X >= 0, the module's text)
     of a batch of pairs of any length (saln_ends_free_xdrop_long_align_batch):
     ends_free_align_batch(..., mode=EXTEND, xdrop=X) without the length limits,
@@ -336,9 +340,15 @@ def xdrop_extend_long_batch(queries, dbs, pairs=None, *, xdrop, scoring=None, tr
     other pair runs the chunked X-drop fill, and its ``reserved`` holds the
     row-loop steps summed over the chunks it ran (``xdrop_steps``).  The only
     limit is the range guard, (n + m + 2) * max|parameter| + X < 2^30.  Codes
-    are sized as under ends_free_align_long_batch (``trace_bytes_long``)."""
-    return _align_batch("saln_ends_free_long_align_batch", queries, dbs, pairs, EXTEND, scoring,
-                        trace_budget, cigar, device, _int_xdrop(xdrop))
+    are sized as under ends_free_align_long_batch (``trace_bytes_long``).
+    replay=True (saln_ends_free_xdrop_replay_align_batch): the same records
+    (``reserved`` may differ: the forward pass's steps) and words, but a pair
+    of the chunked fill holds ``xdrop_replay_bytes`` against trace_budget and
+    its alignment comes from the tiled replay (option ``ends_free.tile_rows``);
+    TRACE_CAP then means that this replay footprint alone exceeds the budget."""
+    entry = "saln_ends_free_replay_align_batch" if replay else "saln_ends_free_long_align_batch"
+    return _align_batch(entry, queries, dbs, pairs, EXTEND, scoring, trace_budget, cigar, device,
+                        _int_xdrop(xdrop))
 
 
 def _one(seq1, seq2, mode, scoring, trace_budget, device, batch=ends_free_align_batch, **kw):
@@ -412,13 +422,15 @@ def extend_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device
 
 
 def xdrop_extend_long(seq1, seq2, *, xdrop, scoring=None, trace_budget: int = 0, device: int = 0,
-                      direction: str = "right"):
+                      direction: str = "right", replay: bool = False):
     """extend_align(..., xdrop=X) for sequences of any length
-    (xdrop_extend_long_batch); direction="left" as there."""
+    (xdrop_extend_long_batch); direction="left" as there.  replay=True: the
+    tiled replay, as there; TRACE_CAP then means the replay footprint
+    (``xdrop_replay_bytes``) exceeds trace_budget."""
     def batch(qs, ds, pairs, *, mode, **kw):
         return xdrop_extend_long_batch(qs, ds, pairs, **kw)
     return _extend(seq1, seq2, direction, scoring, trace_budget, device, batch=batch,
-                   xdrop=_int_xdrop(xdrop))
+                   xdrop=_int_xdrop(xdrop), replay=replay)
 
 
 def local_align_long(seq1, seq2, *, scoring=None, trace_budget: int = 0, device: int = 0,
@@ -530,6 +542,20 @@ def replay_bytes(len_q: int, len_db: int, tile_rows: int = 0) -> int:
     _lib.check(_lib.lib().saln_ends_free_replay_bytes(int(len_q), int(len_db), int(tile_rows),
                                                       C.byref(out)),
                "saln_ends_free_replay_bytes")
+    return out.value
+
+
+def xdrop_replay_bytes(len_q: int, len_db: int, tile_rows: int = 0) -> int:
+    """saln_ends_free_xdrop_replay_bytes: bytes one pair holds against
+    trace_budget under xdrop_extend_long_batch(..., replay=True) (host only).
+    trace_bytes within the class limits; above them a header per chunk, the
+    boundary columns and the checkpoint rows (16 bytes per entry: B is kept
+    too) and one tile of codes, sized for all rows.  tile_rows 0: the value of
+    option ends_free.tile_rows."""
+    out = C.c_uint64()
+    _lib.check(_lib.lib().saln_ends_free_xdrop_replay_bytes(int(len_q), int(len_db), int(tile_rows),
+                                                            C.byref(out)),
+               "saln_ends_free_xdrop_replay_bytes")
     return out.value
 
 
