@@ -143,7 +143,8 @@ int saln_abi_version(void);
  * "nw.spec_passes", "nw.spec_strict", "nw.avsa_narrow", "nw.rows_lone",
  * "nw.rows_xcd", "nw.avsa_profile", "nw.pk_tab", "nw.walk_waves",
  * "nw.timing_mode", "wfa2.seq_lds", "wfa2.w1", "wfa2.w2", "wfa.arena_mb",
- * "ends_free.tile_rows", "host.timing", "host.prefault_mb".
+ * "ends_free.tile_rows", "ends_free.score_i16", "host.timing",
+ * "host.prefault_mb".
  * Two levels, no other shared state:
  *  - saln_option_*: the process registry, the default of every context;
  *  - saln_context_option_*: overrides of one context (its own thread's
@@ -156,6 +157,10 @@ int saln_abi_version(void);
  * The tile-rows option of the ends-free replay traceback is stored within
  * 64..1024, but that entry point runs only 64, 128, 256, 512 and 1024 (see
  * saln_ends_free_replay_align_batch).
+ * The score search's option (score_i16; default 1: the packed-i16 fill where
+ * it fits; 0: the i32 fill for every pair) is stored within 0..2,
+ * but the saln_ends_free_score_* entry points run only 0 and 1 and refuse any
+ * other value with SALN_E_INVALID.
  * The arena option (MB, default 32768, minimum 1) bounds the tensor history
  * that one launch of the reference-semantics WFA (saln_wfa_*) keeps.  A lane
  * (one pair) of a pass with step cap s and width W holds S = s / 2 + 1 tensor
@@ -1198,6 +1203,77 @@ int saln_ends_free_sub_xdrop_replay_align_batch(saln_context *ctx, const uint8_t
                                                 const saln_sub_matrix *matrix, int32_t xdrop,
                                                 uint64_t trace_budget_bytes, int want_cigar,
                                                 saln_ends_free_aln **out);
+
+/* Score-only search (ends_free_score_kernels.hip, ends_free_score_host.cpp):
+ * what does each of these pairs score?  The first step of a database search:
+ * score many pairs, rank, then align the few that matter with the entry
+ * points above.
+ *  - scores[p] is exactly the `score` that saln_ends_free_align_batch gives
+ *    pair p under the same mode and scoring.  Nothing else is reported: no end
+ *    cell, no state.
+ *  - Pair lists, argument errors and the four modes as there; SALN_MODE_GLOBAL
+ *    and every other value are SALN_E_INVALID.  Limits are the class limits
+ *    (1,024 columns, 65,000 rows, the same messages; no long form), and the
+ *    range guard (n + m + 2) * max|parameter| < 2^30 stays in force.
+ *    Arguments are validated before the device is touched.
+ *  - A pair of SALN_MODE_LOCAL or SALN_MODE_SEMI_GLOBAL runs the packed fill,
+ *    16-bit values and two pairs per lane group, when its values fit int16.
+ *    With S+ the largest positive s(i, j) (match, or the matrix's largest
+ *    entry, at least 0) and A the largest |parameter|, gaps included (what
+ *    saln_sub_matrix_check yields), a pair of n columns and m rows is packed
+ *    iff
+ *        min(n, m) * S+ + 4 * A < 2^15                   both modes, and
+ *        (n + 4) * A < 2^15                              semi-global.
+ *    Every other pair, and every pair of SALN_MODE_OVERLAP and
+ *    SALN_MODE_EXTEND, runs the i32 fill of saln_ends_free_plan_create.  The
+ *    score does not depend on the path.  saln_ends_free_score_path is the one
+ *    place the path is decided; the plan asks the same function.
+ *  - Option "ends_free.score_i16": 1 (the default) as above, 0 the i32 fill
+ *    for every pair; any other value makes these entry points SALN_E_INVALID.
+ * saln_ends_free_score_batch: host sequences in, scores[n_pairs] (host) out. */
+int saln_ends_free_score_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
+                               const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
+                               const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                               const saln_nw_scoring *scoring, int32_t *scores);
+int saln_ends_free_sub_score_batch(saln_context *ctx, const uint8_t *q_seq, const uint64_t *q_off, uint64_t n_q,
+                                   const uint8_t *db_seq, const uint64_t *db_off, uint64_t n_db,
+                                   const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
+                                   int32_t mode, const saln_sub_matrix *matrix, int32_t *scores);
+/* Device-resident form: plan from host offsets and a pair list (NULL =
+ * all-vs-all), execute on device sequences (same CSR layout) into device
+ * d_scores[n_pairs], any number of times.  Stream as the other plans.  The
+ * plan owns the workspace of its i32 pairs: its executes must not overlap. */
+typedef struct saln_ends_free_score_plan saln_ends_free_score_plan;
+int saln_ends_free_score_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                     const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                     const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                                     const saln_nw_scoring *scoring, saln_ends_free_score_plan **out);
+int saln_ends_free_sub_score_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q,
+                                         const uint64_t *db_off, uint64_t n_db, const uint32_t *pair_q,
+                                         const uint32_t *pair_db, uint64_t n_pairs, int32_t mode,
+                                         const saln_sub_matrix *matrix, saln_ends_free_score_plan **out);
+int saln_ends_free_score_execute(saln_ends_free_score_plan *plan, const uint8_t *d_q_seq,
+                                 const uint8_t *d_db_seq, int32_t *d_scores, void *stream);
+/* How many of the plan's pairs run the packed fill and how many the i32 fill
+ * (either output may be NULL). */
+int saln_ends_free_score_plan_info(const saln_ends_free_score_plan *plan, uint64_t *packed_pairs,
+                                   uint64_t *i32_pairs);
+int saln_ends_free_score_plan_destroy(saln_ends_free_score_plan *plan);
+/* Host only: *packed = 1 iff a pair of len_q columns and len_db rows runs the
+ * packed fill under `mode` and a scoring with the given S+ (max_pos) and A
+ * (max_abs), by the formula above (option "ends_free.score_i16" not counted).
+ * SALN_E_INVALID for a mode outside the four, above 1,024 columns or 65,000
+ * rows, for a negative max_pos or max_abs and for a NULL output. */
+int saln_ends_free_score_path(uint64_t len_q, uint64_t len_db, int32_t mode, int32_t max_pos, int32_t max_abs,
+                              int32_t *packed);
+/* Host only: the workgroup of a packed launch, saln_ends_free_fill_geometry's
+ * rule for groups that stage two db rows: *groups lane groups (two pairs
+ * each), 256 / lanes of them, lowered until groups * 2 * (ld_max + 2 * lanes)
+ * bytes fit 64 KB (less the matrix block's 1,408 bytes with has_matrix != 0);
+ * never below 1.  *lds_bytes: those bytes.  Errors as there.  The launch code
+ * asks the same function. */
+int saln_ends_free_score_geometry(uint64_t len_q, uint64_t ld_max, int has_matrix, uint32_t *groups,
+                                  uint32_t *lds_bytes);
 
 /* --------------------------------------------------------------------- FASTA
  * Replaces `pub fn parse_fasta(path: PathBuf) -> Result<Records>`

@@ -16,7 +16,7 @@ from .wfa import WfaAlignment, WfaPlan, wfa_align, wfa_align_batch
 from . import wfa_affine
 from .wfa_affine import wfa_affine_align, wfa_affine_align_batch
 from . import ends_free
-from .ends_free import (EndsFreePlan, SubstitutionMatrix, alignment_score, ends_free_align_batch,
+from .ends_free import (EndsFreePlan, EndsFreeScorePlan, SubstitutionMatrix, alignment_score, ends_free_align_batch,
                         ends_free_align_long_batch, extend_align, extend_align_long, local_align, local_align_long, overlap_align,
                         overlap_align_long, semi_global_align, semi_global_align_long, xdrop_extend_long, xdrop_extend_long_batch,
                         xdrop_steps)
@@ -28,7 +28,7 @@ __all__ = [
     "cigar_ops_string", "dense_mask", "n_w_align", "NwAllVsAll", "nw_score_all_vs_all", "nw_align_batch", "pack_csr", "render", "render_batch",
     "wfa", "WfaAlignment", "WfaPlan", "wfa_align", "wfa_align_batch", "wfa_affine",
     "wfa_affine_align", "wfa_affine_align_batch",
-    "ends_free", "EndsFreePlan", "SubstitutionMatrix", "alignment_score", "ends_free_align_batch", "local_align", "semi_global_align",
+    "ends_free", "EndsFreePlan", "EndsFreeScorePlan", "SubstitutionMatrix", "alignment_score", "ends_free_align_batch", "local_align", "semi_global_align",
     "ends_free_align_long_batch", "local_align_long", "semi_global_align_long",
     "overlap_align", "overlap_align_long", "extend_align", "extend_align_long", "xdrop_steps",
     "xdrop_extend_long_batch", "xdrop_extend_long",

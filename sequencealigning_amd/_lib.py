@@ -161,6 +161,10 @@ EXPORTS = [
     "saln_ends_free_xdrop_long_align_batch", "saln_ends_free_sub_xdrop_long_align_batch",
     "saln_ends_free_xdrop_replay_align_batch", "saln_ends_free_sub_xdrop_replay_align_batch",
     "saln_ends_free_xdrop_replay_bytes",
+    "saln_ends_free_score_batch", "saln_ends_free_sub_score_batch",
+    "saln_ends_free_score_plan_create", "saln_ends_free_sub_score_plan_create",
+    "saln_ends_free_score_execute", "saln_ends_free_score_plan_info",
+    "saln_ends_free_score_plan_destroy", "saln_ends_free_score_path", "saln_ends_free_score_geometry",
     "saln_parse_fasta", "saln_parse_fasta_buffer", "saln_records_count", "saln_records_get",
     "saln_records_free",
     "saln_option_set", "saln_option_get", "saln_option_name", "saln_options_reset",
@@ -346,6 +350,17 @@ def lib() -> C.CDLL:
             getattr(L, name + "long_align_batch").argtypes = getattr(L, name + "align_batch").argtypes
             getattr(L, name + "replay_align_batch").argtypes = getattr(L, name + "align_batch").argtypes
         L.saln_ends_free_xdrop_replay_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, u64p]
+        # the score search: the batch's arguments up to the scoring, then the scores
+        L.saln_ends_free_score_batch.argtypes = list(L.saln_ends_free_align_batch.argtypes[:12]) + [i32p]
+        L.saln_ends_free_sub_score_batch.argtypes = list(sub_batch[:12]) + [i32p]
+        L.saln_ends_free_score_plan_create.argtypes = L.saln_ends_free_plan_create.argtypes
+        L.saln_ends_free_sub_score_plan_create.argtypes = sub_plan
+        L.saln_ends_free_score_execute.argtypes = [vp, vp, vp, vp, vp]
+        L.saln_ends_free_score_plan_info.argtypes = [vp, u64p, u64p]
+        L.saln_ends_free_score_plan_destroy.argtypes = [vp]
+        L.saln_ends_free_score_path.argtypes = [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                                i32p]
+        L.saln_ends_free_score_geometry.argtypes = [C.c_uint64, C.c_uint64, C.c_int, u32p, u32p]
         L.saln_parse_fasta.argtypes = [C.c_char_p, C.POINTER(vp), u8p, C.c_uint64, u64p]
         L.saln_parse_fasta_buffer.argtypes = [vp, C.c_uint64, C.POINTER(vp), u8p, C.c_uint64,
                                               u64p]

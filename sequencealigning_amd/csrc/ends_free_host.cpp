@@ -30,10 +30,7 @@ using namespace saln;
 
 namespace {
 
-struct Launch {
-    int cls;
-    uint32_t first, count, ld_max;
-};
+using Launch = EfLaunch;
 
 int bit_bucket(uint32_t v) {
     int b = 0;
@@ -217,6 +214,19 @@ int run_fills(const std::vector<Launch> &launches, int32_t mode, const EfPair *d
 }
 
 }  // namespace
+
+// What the score entry points (ends_free_score_host.cpp) take from this file.
+int saln::ef_check_mode(int32_t mode) { return check_mode(mode); }
+int saln::ef_make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::vector<uint8_t> *block) {
+    return make_scoring(src, out, max_abs, block);
+}
+int saln::ef_check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs) { return check_pair(lq, ld, max_abs); }
+int saln::ef_build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
+                         const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, uint64_t max_abs,
+                         std::vector<EfPair> *out) {
+    return build_pairs(q_off, n_q, db_off, n_db, pair_q, pair_db, n_pairs, max_abs, out);
+}
+void saln::ef_plan_launches(std::vector<EfPair> *pairs, std::vector<EfLaunch> *out) { plan_launches(pairs, out); }
 
 struct saln_ends_free_plan {
     saln_context *ctx = nullptr;

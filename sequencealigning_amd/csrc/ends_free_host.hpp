@@ -7,6 +7,8 @@
 #include "ends_free.hpp"
 #include "host_common.hpp"
 
+#include <vector>
+
 namespace saln {
 
 // A batch's or a plan's scoring as the caller gave it: the scalar scheme
@@ -47,6 +49,23 @@ int ef_plan_create(saln_context *ctx, const uint64_t *q_off, uint64_t n_q, const
                    uint64_t n_db, const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs,
                    int32_t mode, const EfScoreSrc &scoring, saln_ends_free_plan **out,
                    int32_t xdrop = kEfNoXdrop);
+
+// What ends_free_score_host.cpp (saln_ends_free_score_*) takes from
+// ends_free_host.cpp: the mode and scoring checks with their messages, the
+// per-pair limits and range guard, the pair descriptors in pair order, and the
+// class fills' launches (pairs sorted by class and falling db length, cut where
+// the length's power-of-two bucket changes).
+struct EfLaunch {
+    int cls;
+    uint32_t first, count, ld_max;
+};
+int ef_check_mode(int32_t mode);
+int ef_make_scoring(const EfScoreSrc &src, EfScoring *out, uint64_t *max_abs, std::vector<uint8_t> *block);
+int ef_check_pair(uint64_t lq, uint64_t ld, uint64_t max_abs);
+int ef_build_pairs(const uint64_t *q_off, uint64_t n_q, const uint64_t *db_off, uint64_t n_db,
+                   const uint32_t *pair_q, const uint32_t *pair_db, uint64_t n_pairs, uint64_t max_abs,
+                   std::vector<EfPair> *out);
+void ef_plan_launches(std::vector<EfPair> *pairs, std::vector<EfLaunch> *out);
 
 // Device workspace of a batch's chunked fills, all on one stream: the boundary
 // slots (grown to the largest launch's need) and the pair counter.

@@ -30,6 +30,7 @@ const OptDesc kDesc[kNumOpts] = {
     {"wfa2.w2", 0, 0, 4096},
     {"wfa.arena_mb", 32 * 1024, 1, int64_t(1) << 30},
     {"ends_free.tile_rows", 1024, 64, 1024},
+    {"ends_free.score_i16", 1, 0, 2},
     {"host.timing", 0, 0, 1},
     {"host.prefault_mb", 0, 0, 1 << 16},
 };

@@ -36,6 +36,7 @@ enum class Opt : int {
     Wfa2W2,             // "wfa2.w2": second-pass ring width (0 auto)
     WfaArenaMb,         // "wfa.arena_mb": MB of tensor history per launch (reference-semantics WFA)
     EndsFreeTileRows,   // "ends_free.tile_rows": db rows of a tile of the replay traceback (64, 128, 256, 512, 1024)
+    EndsFreeScoreI16,   // "ends_free.score_i16": the score entry points' packed-i16 fill where it fits (1, the default) or the i32 fill for every pair (0); stored within 0..2, 2 is refused there
     HostTiming,         // "host.timing": stage times of the host paths on stderr
     HostPrefaultMb,     // "host.prefault_mb": host buffer a new context faults in while HIP starts
     Count

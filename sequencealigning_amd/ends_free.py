@@ -63,6 +63,13 @@ trace codes and its alignment is walked tile by tile
 ``trace_budget``, option ``ends_free.tile_rows`` the tile's db rows).  Records
 and words are the same.
 
+``score_batch`` and ``EndsFreeScorePlan`` (``saln_ends_free_score_*``) answer a
+search's first question, what each pair scores, and nothing else: one int32 per
+pair, exactly ``ends_free_align_batch``'s ``score``, in all four modes.  Local
+and semi-global pairs whose values fit 16 bits (``score_path``) run the
+packed-i16 fill (ends_free_score_kernels.hip), two pairs to a lane group; every
+other pair runs the i32 fill.  Same length limits as ``ends_free_align_batch``.
+
 Every ``scoring=`` argument takes the 4-tuple above or a ``SubstitutionMatrix``
 (protein scoring under a BLOSUM or PAM style table, IUPAC codes, transition /
 transversion scoring): s(i, j) = scores[symbol of the db byte][symbol of the
@@ -592,6 +599,117 @@ def fill_geometry(len_q: int, ld_max: int, has_matrix: bool = False) -> tuple[in
                                                        C.byref(groups), C.byref(lds)),
                "saln_ends_free_fill_geometry")
     return groups.value, lds.value
+
+
+def _score_limits(scoring):
+    """(S+, A) of a scoring for score_path: the largest positive s(i, j) and
+    the largest |parameter|, gaps included."""
+    if isinstance(scoring, SubstitutionMatrix):
+        flat = [v for r in scoring.table for v in r]
+        return max(0, max(flat)), scoring.check()
+    sc = tuple(int(v) for v in (scoring if scoring is not None else DEFAULT_SCORING))
+    return max(0, sc[0]), max(abs(v) for v in sc)
+
+
+def score_path(len_q: int, len_db: int, mode, scoring=None) -> bool:
+    """saln_ends_free_score_path (host only): does a pair of len_q columns and
+    len_db rows run the packed-i16 fill of score_batch / EndsFreeScorePlan
+    under this mode and scoring (the 4-tuple or a SubstitutionMatrix)?  Local
+    and semi-global only, and only while min(n, m) * S+ + 4 * A < 2^15 and, in
+    semi-global, (n + 4) * A < 2^15; every other pair runs the i32 fill.  Option
+    ``ends_free.score_i16`` = 0 sends every pair there and is not counted here.
+    Raises SalnError (E_INVALID) above MAX_QUERY columns or 65,000 rows."""
+    pos, mx = _score_limits(scoring)
+    out = C.c_int32()
+    _lib.check(_lib.lib().saln_ends_free_score_path(int(len_q), int(len_db), _mode(mode), pos, mx,
+                                                    C.byref(out)), "saln_ends_free_score_path")
+    return bool(out.value)
+
+
+def score_geometry(len_q: int, ld_max: int, has_matrix: bool = False) -> tuple[int, int]:
+    """saln_ends_free_score_geometry (host only): (lane groups per workgroup,
+    two pairs each; bytes of LDS their staged db rows take) of the packed fill
+    that runs queries of len_q columns in a launch whose longest db has ld_max
+    rows: fill_geometry's rule over rows of twice the bytes."""
+    groups, lds = C.c_uint32(), C.c_uint32()
+    _lib.check(_lib.lib().saln_ends_free_score_geometry(int(len_q), int(ld_max), int(bool(has_matrix)),
+                                                        C.byref(groups), C.byref(lds)),
+               "saln_ends_free_score_geometry")
+    return groups.value, lds.value
+
+
+def score_batch(queries, dbs, pairs=None, *, mode, scoring=None, device: int = 0) -> np.ndarray:
+    """The scores of a batch and nothing else (saln_ends_free_score_batch): the
+    first step of a search, before the few pairs that matter are aligned.
+    Returns int32[n_pairs]: exactly the ``score`` that ends_free_align_batch
+    gives each pair under the same mode (any of the four) and scoring (the
+    4-tuple or a SubstitutionMatrix).  pairs as there.  Local and semi-global
+    pairs whose values fit 16 bits (score_path) run two to a lane group in the
+    packed fill; every other pair runs the i32 fill.  Limits: MAX_QUERY columns
+    and 65,000 rows."""
+    qs, qo = pack_csr(queries)
+    ds, do = pack_csr(dbs)
+    pq, pd, n = _pair_lists(pairs, len(qo) - 1, len(do) - 1)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    entry, sarg = _scoring_entry("saln_ends_free_score_batch", scoring)
+    scores = np.zeros(max(n, 1), np.int32)
+    _lib.check(getattr(_lib.lib(), entry)(
+        _lib.context(device), vp(qs), vp(qo), len(qo) - 1, vp(ds), vp(do), len(do) - 1, vp(pq), vp(pd), n,
+        _mode(mode), sarg, scores.ctypes.data_as(C.POINTER(C.c_int32))), entry)
+    return scores[:n]
+
+
+class EndsFreeScorePlan:
+    """Device-resident score search (saln_ends_free_score_plan_create): plan
+    from host offsets and a pair list once, execute any number of times on
+    device (torch) sequence buffers into a device int32 tensor of n_pairs
+    scores, each the ``score`` of ends_free_align_batch.  scoring: the 4-tuple
+    or a SubstitutionMatrix.  ``info()``: how many pairs run the packed-i16 fill
+    and how many the i32 fill (score_path; option ``ends_free.score_i16`` = 0,
+    read when the plan is created, sends all to i32).  The plan owns the i32
+    pairs' workspace: its executes must not overlap."""
+
+    def __init__(self, q_off, db_off, pairs=None, *, mode, scoring=None, device: int = 0):
+        L = _lib.lib()
+        self._L = L
+        self.device = device
+        qo = np.ascontiguousarray(q_off, np.uint64)
+        do = np.ascontiguousarray(db_off, np.uint64)
+        pq, pd, n = _pair_lists(pairs, len(qo) - 1, len(do) - 1)
+        self.n_pairs = n
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        self._h = C.c_void_p()
+        entry, sarg = _scoring_entry("saln_ends_free_score_plan_create", scoring)
+        _lib.check(getattr(L, entry)(_lib.context(device), vp(qo), len(qo) - 1, vp(do), len(do) - 1,
+                                     vp(pq), vp(pd), n, _mode(mode), sarg, C.byref(self._h)), entry)
+
+    def execute(self, d_q, d_db, d_scores, stream=None):
+        """d_q / d_db: device uint8 tensors (CSR bytes), d_scores: device
+        int32[n_pairs]."""
+        assert d_scores.numel() * d_scores.dtype.itemsize >= 4 * self.n_pairs
+        if stream is None:  # torch's current stream, like EndsFreePlan.execute
+            stream = _lib.torch_stream(d_scores.device)
+        _lib.check(self._L.saln_ends_free_score_execute(
+            self._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_db.data_ptr()),
+            C.c_void_p(d_scores.data_ptr()), C.c_void_p(stream)), "saln_ends_free_score_execute")
+
+    def info(self) -> tuple[int, int]:
+        """(pairs of the packed fill, pairs of the i32 fill)."""
+        pk, i32 = C.c_uint64(), C.c_uint64()
+        _lib.check(self._L.saln_ends_free_score_plan_info(self._h, C.byref(pk), C.byref(i32)),
+                   "saln_ends_free_score_plan_info")
+        return pk.value, i32.value
+
+    def close(self):
+        if self._h:
+            self._L.saln_ends_free_score_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class EndsFreePlan:
